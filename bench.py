@@ -74,7 +74,13 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="time the eager launches only (skip the HIP-graph replay of the train step)")
     ap.add_argument("--graph-ddp", action="store_true",
                     help="also try the HIP-graph step when a process group is active (the RCCL collectives are then captured too)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="vae_train: after the timed steps, write what the last timed step of each launch mode returned (its losses, "
+                         "float64) and the parameters it wrote (float32, a fixed seeded sample) to DIR/<mode>_<name>.npy "
+                         "(bench_outputs/ is git-ignored)")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.workload != "vae_train":
+        ap.error("--dump-outputs is implemented for --workload vae_train")
     if args.batch is None:
         args.batch = 4 if args.workload == "dit_train" else 1
     dsteps, dwarm = {"vae_train": (3, 1), "dit_sample": (50, 5), "dit_train": (5, 2), "long_context": (6, 2)}[args.workload]
@@ -1303,6 +1309,36 @@ def emit(line):
     out.flush()
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_PARAM_SAMPLE = 1 << 22     # parameters kept per dumped step: 16 MiB of float32 (the VAE has ~157 M)
+
+
+def step_outputs(out, flat, sample=DUMP_PARAM_SAMPLE, seed=0):
+    """What one train step hands its caller, copied to the host: every loss of the returned dict (float64) and the parameters the
+    step wrote (float32; the same seeded sample of `sample` positions on every run when the model is larger).  Read right after the
+    step: a replayed step returns the graph's static buffers."""
+    res = {k: v.detach().double().cpu().numpy() for k, v in sorted(out.items())}
+    data = flat.data[:flat.numel]
+    if data.numel() > sample:
+        idx = torch.randint(0, data.numel(), (sample,), generator=torch.Generator().manual_seed(seed)).sort().values
+        data = data[idx.to(data.device)]
+    res["params"] = data.cpu().numpy()
+    return res
+
+
+def write_outputs(dirpath, by_mode):
+    """by_mode: {launch mode: step_outputs(...)} -> dirpath/<mode>_<name>.npy.  Returns the file names."""
+    import numpy as np
+    arrays = {f"{mode}_{name}": a for mode, res in by_mode.items() for name, a in res.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: {total} bytes > {DUMP_BUDGET_BYTES}"
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    return sorted(n + ".npy" for n in arrays)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1394,6 +1430,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss = float(out["loss"])
+    dumped = {"eager": step_outputs(out, stepper.flat)} if args.dump_outputs is not None else None
     ddp_timeline = stepper.comm.timeline()
     stepper.comm.timing = False
     elapsed_eager = elapsed
@@ -1420,6 +1457,8 @@ def main():
             t = torch.tensor([elapsed_graph], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed_graph = float(t.item())
+        if dumped is not None:
+            dumped["hip_graph"] = step_outputs(out_g, stepper.flat)
         launch["ms_per_step"]["hip_graph"] = 1e3 * elapsed_graph / args.steps
         launch["graph_replays"] = gstep.replays
         if gstep.fallback:
@@ -1443,6 +1482,7 @@ def main():
             elapsed = elapsed_graph
             launch["mode"] = "hip_graph"
         launch["value_uses"] = launch["mode"]
+    dump_files = write_outputs(args.dump_outputs, dumped) if dumped is not None and rank == 0 else None
 
     if dist.is_initialized():      # the line's n_gpus IS the size of the process group the exchange ran in
         assert dist.get_world_size() == world == args.gpus, (dist.get_world_size(), world, args.gpus)
@@ -1651,6 +1691,8 @@ def main():
                 line["long_context"] = long_context_line(with_cpu_baseline=not args.no_cpu_baseline)
             if not args.no_dit_train:
                 line["dit_train"] = dit_train_object(with_cpu_baseline=not args.no_cpu_baseline)
+        if dump_files is not None:
+            line["config"]["dump_outputs"] = {"dir": args.dump_outputs, "files": dump_files}
         emit(line)
     if dist.is_initialized():
         dist.destroy_process_group()

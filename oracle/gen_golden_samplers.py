@@ -11,9 +11,11 @@ REFERENCE's DiffusionTransformer, run on CPU in the build container:
 
 Weights, inputs and the noise streams are regenerated from seeds (oracle/seeded.py, oracle/gen_golden.dit_inputs, torch.manual_seed);
 only outputs are committed: tests/golden/samplers.npz.  Each entry also records the per-step `denoised` the reference hands to
-its callback (first batch item, first channel) so that the fused update's second output is pinned too.
+its callback (first batch item, first channel) so that the fused update's second output is pinned too.  The reference's
+DistributionShift.time_shift over a small grid goes to tests/golden/sampler_shift.npz.
 
-    python oracle/gen_golden_samplers.py
+    python oracle/gen_golden_samplers.py                # both files
+    python oracle/gen_golden_samplers.py --shift-only   # sampler_shift.npz alone
 """
 import contextlib
 import os
@@ -51,6 +53,17 @@ CASES = {
     "rf_dpmpp":     ("small_rf", 720, "sample_rf", dict(steps=5, sampler_type="dpmpp", sigma_max=0.8, device="cpu", with_init=True), GUIDE_RF),
     "rf_rk4":       ("small_rf", 720, "sample_rf", dict(steps=2, sampler_type="rk4", device="cpu"), GUIDE_RF),
 }
+
+
+# DistributionShift.time_shift grid (tests/golden/sampler_shift.npz): constructor keywords x sequence lengths
+SHIFT_KWARGS = (dict(), dict(use_sine=True), dict(base_shift=0.3, max_shift=2.0, max_length=1000, min_length=10))
+SHIFT_LENGTHS = (8, 300, 5000)
+
+
+def shift_table(sampling):
+    """time_shift outputs of `sampling.DistributionShift` over the grid, keyed "<kwargs index>/<seq_len>"."""
+    t = torch.linspace(0.97, 0, 9)
+    return {f"{i}/{n}": sampling.DistributionShift(**kw).time_shift(t, n) for i, kw in enumerate(SHIFT_KWARGS) for n in SHIFT_LENGTHS}
 
 
 def case_kwargs(kw, shift_cls):
@@ -108,6 +121,9 @@ def main():
     with contextlib.redirect_stdout(sys.stderr):
         refimport.import_reference()
     import stable_audio_tools.inference.sampling as ref_sampling
+    np.savez_compressed(os.path.join(OUT, "sampler_shift.npz"), **{k: v.numpy() for k, v in shift_table(ref_sampling).items()})
+    if "--shift-only" in sys.argv:
+        return
     torch.set_num_threads(8)
     models, out = {}, {}
     for case, (name, seed, *_rest) in CASES.items():
