@@ -6,16 +6,23 @@ the Oobleck audio VAE on 47.55 s stereo 44.1 kHz items (sample_size 2097152): en
 decode -> multi-resolution STFT loss (sum/diff + L + R, 7 resolutions, A-weighted) + KL -> backward ->
 data-parallel gradient all-reduce -> fused AdamW (+EMA).  fp32, synthetic audio, random-init weights of
 the stable_audio_2_0_vae architecture.  `value` times that generator step (comparable across rounds and
-across N).  The reference's REAL step alternates it with the MS-STFT discriminator update
-(training/autoencoders.py:440-515): that is built too and timed in the same run on the
-same items — top-level `real_step_samples_per_s` / `real_step_ms`, details in `config.real_step`.
+across N).
 
-The same line carries `roofline` (dominant kernel, HIP events), `cpu_baseline` (ONE un-scaled generator
-step of the REFERENCE's own modules on this box's host cores — oracle/stage_ref.py ships the reference
-tree to the GPU box), `parity` (the bench item against the CPU oracle), `secondary` (the metric's second
-half: DiT sampling steps/s, configs[2]) and `long_context` (configs[4] on one GPU).
+A plain run does what that figure needs and no more: set-up, the warm-up and timed steps (eager launches,
+then the same steps replayed from a HIP graph), `--dump-outputs`, the line.  Its `roofline` (dominant
+kernel) comes from HIP events recorded in the timed eager steps and from committed counter profiles, so
+it costs no run of its own.
 
-Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 launched by torch.distributed.run
+`--full` adds everything else the line can carry, each leg a run of its own after the headline's steps:
+the reference's REAL step, which alternates the generator step with the MS-STFT discriminator update
+(training/autoencoders.py:440-515) on the same items — top-level
+`real_step_samples_per_s` / `real_step_ms`, details in `config.real_step`; `config.batch_sweep`;
+`cpu_baseline` (ONE un-scaled generator step of the REFERENCE's own modules on the host cores, from the
+tree oracle/stage_ref.py staged); `parity` (the bench item against the CPU oracle); `secondary` (the
+metric's second half: DiT sampling steps/s, configs[2]); `long_context` (configs[4] on one GPU) and
+`dit_train`.  The other workloads keep their CPU baselines and parity evaluations behind `--full` too.
+
+Contract: `python bench.py --gpus N --steps K --warmup W [--full]`; for N>1 launched by torch.distributed.run
 (one rank per GPU, RCCL).  Rank 0 prints ONE JSON line.  `--ddp-single-rank` runs the N=1 step inside a
 1-rank RCCL process group with the overlapped gradient exchange forced on (the P1 path on a 1-GPU box).
 """
@@ -37,7 +44,11 @@ SAMPLE_SIZE = 2097152
 PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak (= fp32 vector peak)
 
 
-def parse():
+# the legs of the line that only `--full` runs (each has a --no-<leg> option that drops it from a full run)
+FULL_ONLY_LEGS = ("cpu_baseline", "real_step", "secondary", "long_context", "dit_train", "batch_sweep", "parity")
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 3 vae_train, 50 dit_sample, 5 dit_train)")
@@ -45,15 +56,20 @@ def parse():
     ap.add_argument("--batch", type=int, default=None,
                     help="items per GPU per step (default: 1 for vae_train and dit_sample, 4 for dit_train)")
     ap.add_argument("--sample-size", type=int, default=SAMPLE_SIZE)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-real-step", action="store_true", help="skip the timing of the alternating discriminator / generator step")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the DiT sampling measurement appended to the default line")
-    ap.add_argument("--no-long-context", action="store_true", help="skip the N = 6145 fp8 sampling measurement (BASELINE.json configs[4])")
-    ap.add_argument("--no-dit-train", action="store_true", help="skip the DiT training-step measurement appended to the default line (configs[2]/[3])")
-    ap.add_argument("--no-batch-sweep", action="store_true", help="skip the generator step at per-GPU batch 2 and 4 (config.batch_sweep)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle parity check of the bench item (about one CPU-minute)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's steps, also run everything else the line can carry: the batch sweep, the CPU baselines, the "
+                         "oracle parity checks, the alternating discriminator / generator step, the DiT sampling, long-context and DiT "
+                         "training measurements (minutes; the --no-* options below drop single legs of it).  Without it a run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines (and the DiT parity evaluations that ride on them)")
+    ap.add_argument("--no-real-step", action="store_true", help="--full: skip the timing of the alternating discriminator / generator step")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the DiT sampling measurement appended to the full line")
+    ap.add_argument("--no-long-context", action="store_true", help="--full: skip the N = 6145 fp8 sampling measurement (BASELINE.json configs[4])")
+    ap.add_argument("--no-dit-train", action="store_true", help="--full: skip the DiT training-step measurement appended to the full line (configs[2]/[3])")
+    ap.add_argument("--no-batch-sweep", action="store_true", help="--full: skip the generator step at per-GPU batch 2 and 4 (config.batch_sweep)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle parity check of the bench item (about one CPU-minute)")
     ap.add_argument("--no-parity-gradients", action="store_true",
-                    help="parity: forward quantities only (skip the oracle's autograd pass over the full item: ~1.5 CPU-minutes, +41 GiB host memory)")
+                    help="--full parity: forward quantities only (skip the oracle's autograd pass over the full item: ~1.5 CPU-minutes, +41 GiB host memory)")
     ap.add_argument("--cpu-baseline-samples", type=int, default=32768, help="length of the probe crop that picks the thread count")
     ap.add_argument("--cpu-baseline-budget-s", type=float, default=100.0,
                     help="time budget of the ONE un-scaled CPU reference step (the full item when it fits, else the largest 1/2^k of it)")
@@ -78,9 +94,12 @@ def parse():
                     help="vae_train: after the timed steps, write what the last timed step of each launch mode returned (its losses, "
                          "float64) and the parameters it wrote (float32, a fixed seeded sample) to DIR/<mode>_<name>.npy "
                          "(bench_outputs/ is git-ignored)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.dump_outputs is not None and args.workload != "vae_train":
         ap.error("--dump-outputs is implemented for --workload vae_train")
+    if not args.full:       # a plain run is the headline alone: every leg beside it is off, whatever the --no-* options say
+        for leg in FULL_ONLY_LEGS:
+            setattr(args, "no_" + leg, True)
     if args.batch is None:
         args.batch = 4 if args.workload == "dit_train" else 1
     dsteps, dwarm = {"vae_train": (3, 1), "dit_sample": (50, 5), "dit_train": (5, 2), "long_context": (6, 2)}[args.workload]
@@ -1497,8 +1516,10 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32(bf16x3)", "data": "synthetic",
             "config": {"workload": "oobleck_vae_generator_train_step(encode+vae_sample+decode+mrstft_sumdiff_LR_7res_aweighted+kl,"
-                                   " backward, dp_allreduce, fused_adamw_ema); stable_audio_2_0_vae architecture, random init;"
-                                   " the alternating MS-STFT-discriminator / generator step of the reference is timed beside it: real_step_*",
+                                   " backward, dp_allreduce, fused_adamw_ema); stable_audio_2_0_vae architecture, random init"
+                                   + ("; the alternating MS-STFT-discriminator / generator step of the reference is timed beside it: real_step_*"
+                                      if stepper.discriminator is not None else ""),
+                       "full": bool(args.full),
                        "sample_size": args.sample_size, "channels": 2, "sample_rate": 44100,
                        "per_gpu_batch": args.batch, "global_batch": args.batch * world,
                        "parallelism": f"dp{world}", "final_loss": loss, "launch": launch, "ops_set": list(args.ops_set),

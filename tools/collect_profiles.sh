@@ -6,7 +6,7 @@
 #   pmc_{FETCH,WRITE}_SIZE.txt + pmc_traffic.json   per-kernel HBM counters of the same bench command (separate passes)
 #   pmc_sq_{vae,dit_train,dit_sample,long_context}.json   MFMA-busy / VALU:MFMA / wait fractions per kernel (tools/pmc_mfma_busy.py)
 #   dit_train_b{4,16}_stats.csv           rocprofv3 kernel summary of bench.py --workload dit_train
-#   bench_*.json                          the bench lines themselves (the default line with cpu_baseline, parity, real step, secondary ...)
+#   bench_*.json                          the bench lines themselves (the `--full` line with cpu_baseline, parity, real step, secondary ...)
 # One call of ~20 GPU-minutes; A/B experiments live with their run scripts under profiles/r0N_experiments/.
 set -u
 R=$(pwd)
@@ -18,7 +18,7 @@ if ! timeout 300 python __graft_entry__.py smoke > $OUT/smoke_first.log 2>&1; th
 cd /tmp && export TMPDIR=/tmp
 GEN="--no-cpu-baseline --no-real-step --no-secondary --no-parity --no-long-context --no-batch-sweep"
 timeout -k 20 400 rocprofv3 --kernel-trace --stats -d $OUT/vae -- python $R/bench.py --steps 3 --warmup 1 $GEN > $OUT/vae_prof.log 2>&1
-timeout -k 20 400 rocprofv3 --kernel-trace --stats -d $OUT/real -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-parity --no-long-context --no-batch-sweep --no-graph > $OUT/real_prof.log 2>&1
+timeout -k 20 400 rocprofv3 --kernel-trace --stats -d $OUT/real -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-parity --no-long-context --no-batch-sweep --no-graph > $OUT/real_prof.log 2>&1
 timeout -k 20 400 rocprofv3 --kernel-trace --stats -d $OUT/dit_sample -- python $R/bench.py --workload dit_sample --steps 10 --warmup 2 --no-cpu-baseline > $OUT/dit_sample_prof.log 2>&1
 timeout -k 20 400 rocprofv3 --kernel-trace --stats -d $OUT/long_context -- python $R/bench.py --workload long_context --steps 4 --warmup 1 --no-cpu-baseline > $OUT/long_context_prof.log 2>&1
 for b in 4 16; do
@@ -46,7 +46,7 @@ rm -rf $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE $OUT/vae $OUT/real $OUT/dit_sampl
 # (these copies live on the GPU box only — bench.py reads them there for roofline.traffic / mfma_utilisation; gpurun brings back gpurun_out/ alone, so
 #  after the call copy gpurun_out/final/{pmc_traffic,pmc_sq_*}.json over profiles/r06_pmc_{traffic,mfma_*}.json by hand, with the other files)
 cp $OUT/pmc_traffic.json $R/profiles/r06_pmc_traffic.json; cp $OUT/pmc_sq_vae.json $R/profiles/r06_pmc_mfma_vae.json; cp $OUT/pmc_sq_dit_train.json $R/profiles/r06_pmc_mfma_dit_train.json; cp $OUT/pmc_sq_dit_sample.json $R/profiles/r06_pmc_mfma_dit_sample.json; cp $OUT/pmc_sq_long_context.json $R/profiles/r06_pmc_mfma_long_context.json      # bench.py reads it for roofline.traffic / roofline.hbm
-timeout 900 python bench.py > $OUT/bench_vae_train.json 2> $OUT/bench_vae_train.err
+timeout 900 python bench.py --full > $OUT/bench_vae_train.json 2> $OUT/bench_vae_train.err
 timeout 300 python bench.py --workload dit_train --no-cpu-baseline > $OUT/bench_dit_train.json 2> /dev/null
 tail -8 $OUT/gpu_tests.log
 tail -c 2500 $OUT/bench_vae_train.json
