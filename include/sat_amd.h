@@ -191,6 +191,25 @@ int sat_conv_wgrad7_bf16x3(const float* dy, const float* x, const float* alpha, 
 int sat_conv_wgrad7_bf16x3_nsplit(int B, int M, int N, int T);
 int sat_conv_wgrad7_bf16x3_fuses_rowsum(int B, int M, int N, int T);
 
+/* The same weight gradient with BOTH operands as pre-split bf16 planes (csrc/conv_wgrad7_planes.h): dy_hi / dy_lo = the hi / lo split of
+ * dy as [B][ceil(M/8)][rows_dy][8], act_hi / act_lo = the split of act(x) as [B][ceil(N/8)][rows_act][8] — the layout of
+ * sat_conv1d_k7_planes (row 32 + t, zero rows around the sequence; the zero rows are the conv's padding).  LDS-DMA + transposed LDS
+ * reads (ds_read_b64_tr_b16), nothing converted in the kernel.  sat_conv_wgrad7_planes_ok: 1 if the shape is served (N >= 64, dilation
+ * 1 / 3 / 9, pad <= 32, enough plane rows), else 0 — the caller then keeps sat_conv_wgrad7_bf16x3.  Slabs as sat_conv_wgrad7_bf16x3
+ * (count from sat_conv_wgrad7_planes_nsplit).  No bias row sums.
+ * Contract of caller-made planes: EVERY row of EVERY chunk holds finite data (the kernel reads whole 64-row pieces, channel chunks past
+ * M / N clamped to the last one, and multiplies what it reads: 0 * NaN would poison dW), rows outside [32, 32 + T) hold zeros, and so do
+ * the channels past M / N inside the last chunk — what sat_conv1d_k7_planes writes, or a zero-filled buffer whose rows 32 .. 32 + T - 1
+ * a producer's plane emission fills. */
+int sat_conv_wgrad7_planes_ok(int B, int M, int N, int T, int dil, int pad, int rows_dy, int rows_act);
+int sat_conv_wgrad7_planes_nsplit(int B, int M, int N, int T);
+int sat_conv_wgrad7_planes(const short* dy_hi, const short* dy_lo, int rows_dy, const short* act_hi, const short* act_lo, int rows_act,
+                           float* partial, long long so_m, long long so_n, long long so_k, int B, int M, int N, int T, int dil, int pad,
+                           void* stream);
+/* Test probe of the transposed LDS read: one wave, image = 1024 16-bit elements copied to LDS, lane l reads at byte offset lane_off[l]
+ * (8-byte aligned, <= 2040), out[4 l + q] = its element q. */
+int sat_lds_read_tr16_probe(const short* image, const int* lane_off, short* out, void* stream);
+
 /* sat_conv_wgrad for K == 1 (stride 1; the k1 conv of every ResidualUnit) and K == 2*stride with a power-of-two stride
  * (the down / up convs, autoencoders.py:245-247, :266-268) on the bf16 matrix cores at fp32 accuracy.  Same arguments as
  * sat_conv_wgrad (dilation 1); slab stride M*N*K; nsplit from sat_conv_wgrad_bf16x3_nsplit (-1: unsupported shape).
@@ -208,7 +227,8 @@ int sat_conv_wgrad_bf16x3_nsplit(int B, int M, int N, int Tlo, int K, int stride
  *   dw_partial [nsplit][C][C]  : slabs of dW2 (torch layout (Cout, Cin, 1)); sum with sat_reduce_splits
  *   part [4][C][nsplit]        : per-split sums of d log-alpha2, d log-beta2, dh (= bias gradient of the k7 conv), dy (= bias
  *                                gradient of the 1x1 conv); sum the last axis (sat_rowsum)
- * wt_hi / wt_lo: W2^T as bf16 hi / lo planes [ci][co] (sat_ru_k1_pack of the (C, C) weight).  All pointers 16-byte aligned. */
+ * wt_hi / wt_lo: W2^T as bf16 hi / lo planes [ci][co] (sat_ru_k1_pack of the (C, C) weight).  All pointers 16-byte aligned.
+ * dh may be NULL when em_hi / em_lo are given: the fp32 dh store is skipped (both consumers of dh read its planes). */
 int sat_ru_k1_bwd_nsplit(int B, int C, int T);
 int sat_ru_k1_pack(const float* w, short* hi, short* lo, int C, void* stream);
 int sat_ru_k1_bwd(const float* dy, const float* h, const short* wt_hi, const short* wt_lo, const float* alpha2, const float* beta2,

@@ -294,6 +294,77 @@ extern "C" int sat_conv_wgrad7_bf16x3(const float* dy, const float* x, const flo
     return sat_check_launch("sat_conv_wgrad7_bf16x3");
 }
 
+#include "conv_wgrad7_planes.h"          // the same gradient from bf16 planes: LDS-DMA + transposed fragment reads, nothing converted
+
+// sat_lds_read_tr16_b64 on its own (tests): one wave copies `image` (1024 16-bit elements) to LDS, lane l reads at byte offset
+// lane_off[l] (8-byte aligned, <= 2040) and stores its four elements to out[4 l ..].
+struct SatTrProbeParams { const short* image; const int* lane_off; short* out; };
+__global__ void __launch_bounds__(64) sat_lds_read_tr16_probe_kernel(SatTrProbeParams p) {
+    __shared__ __attribute__((aligned(16))) short img[1024];
+    const int lane = threadIdx.x;
+    for (int i = lane; i < 1024; i += 64) img[i] = p.image[i];
+    __syncthreads();
+    const bf16x4 v = sat_lds_read_tr16_b64(reinterpret_cast<const char*>(img) + p.lane_off[lane]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p.out[4 * lane + e] = v[e];
+}
+extern "C" int sat_lds_read_tr16_probe(const short* image, const int* lane_off, short* out, void* stream) {
+    if (!image || !lane_off || !out) { sat_set_error("sat_lds_read_tr16_probe: missing buffer"); return 1; }
+    SatTrProbeParams p{image, lane_off, out};
+    SAT_LAUNCH(sat_lds_read_tr16_probe_kernel, dim3(1), dim3(64), stream, p);
+    return sat_check_launch("sat_lds_read_tr16_probe");
+}
+
+// May sat_conv_wgrad7_planes serve this shape?  dy planes [B][ceil(M/8)][rows_dy][8], act planes [B][ceil(N/8)][rows_act][8] (row 32 + t,
+// zero rows around the sequence): a stage reads dy rows [32 + t0, 32 + t0 + 64) and act rows [32 + t0 - pad, 32 + t0 - pad + 128).
+extern "C" int sat_conv_wgrad7_planes_ok(int B, int M, int N, int T, int dil, int pad, int rows_dy, int rows_act) {
+    if (B <= 0 || M <= 0 || N < SAT_WQ_NI || T <= 0) return 0;
+    if ((dil != 1 && dil != 3 && dil != 9) || pad < 0 || pad > SAT_WQ_LEAD) return 0;
+    const int nT = sat_cdiv(T, SAT_WB_TT);
+    if (rows_dy < SAT_WQ_LEAD + nT * SAT_WB_TT) return 0;
+    if (rows_act < SAT_WQ_LEAD + (nT - 1) * SAT_WB_TT - pad + 128) return 0;
+    if (rows_act < SAT_WQ_LEAD + T + 6 * dil - pad) return 0;        // the trailing zero rows cover the last taps
+    return 1;
+}
+static void sat_wgpl_plan(int B, int M, int N, int T, SatWgBfPlan* pl) {          // the pipelined kernel's rule (sat_wgbf_plan)
+    pl->nT = sat_cdiv(T, SAT_WB_TT);
+    pl->nchunks = B * pl->nT;
+    pl->pipe = true;
+    const int tiles = sat_cdiv(M, SAT_CO_T) * sat_cdiv(N, SAT_WQ_NI);
+    int want = 512 / tiles;
+    if (want > pl->nchunks) want = pl->nchunks;
+    if (want < 1) want = 1;
+    pl->cps = sat_cdiv(pl->nchunks, want);
+    pl->nsplit = sat_cdiv(pl->nchunks, pl->cps);
+}
+extern "C" int sat_conv_wgrad7_planes_nsplit(int B, int M, int N, int T) {
+    if (B <= 0 || M <= 0 || N <= 0 || T <= 0) return -1;
+    SatWgBfPlan pl;
+    sat_wgpl_plan(B, M, N, T, &pl);
+    return pl.nsplit;
+}
+// sat_conv_wgrad7_bf16x3 with both operands as planes: dy_hi / dy_lo = split(dy), act_hi / act_lo = split(act(x)) (conv1d_planes.h).
+// Writes sat_conv_wgrad7_planes_nsplit slabs (element (m, n, k) at m*so_m + n*so_n + k*so_k, slab stride M*N*7).
+extern "C" int sat_conv_wgrad7_planes(const short* dy_hi, const short* dy_lo, int rows_dy, const short* act_hi, const short* act_lo,
+                                      int rows_act, float* partial, long long so_m, long long so_n, long long so_k, int B, int M, int N,
+                                      int T, int dil, int pad, void* stream) {
+    if (!dy_hi || !dy_lo || !act_hi || !act_lo || !partial) { sat_set_error("sat_conv_wgrad7_planes: missing buffer"); return 1; }
+    if (!sat_conv_wgrad7_planes_ok(B, M, N, T, dil, pad, rows_dy, rows_act)) {
+        sat_set_error("sat_conv_wgrad7_planes: shape outside the kernel's contract (sat_conv_wgrad7_planes_ok)");
+        return 1;
+    }
+    if ((((uintptr_t)dy_hi | (uintptr_t)dy_lo | (uintptr_t)act_hi | (uintptr_t)act_lo) & 15) != 0) { sat_set_error("sat_conv_wgrad7_planes: planes must be 16-byte aligned"); return 1; }
+    SatWgBfPlan pl;
+    sat_wgpl_plan(B, M, N, T, &pl);
+    SatWgPlParams p{dy_hi, dy_lo, act_hi, act_lo, partial, (long long)M * N * 7, so_m, so_n, so_k, B, M, N, T, pad, rows_dy, rows_act,
+                    sat_cdiv(M, 8), sat_cdiv(N, 8), pl.cps, pl.nchunks, pl.nT};
+    dim3 grid(sat_cdiv(M, SAT_CO_T), sat_cdiv(N, SAT_WQ_NI), pl.nsplit);
+    if (dil == 1) SAT_LAUNCH((sat_wgrad7_planes_kernel<1>), grid, dim3(SAT_WQ_NT), stream, p);
+    else if (dil == 3) SAT_LAUNCH((sat_wgrad7_planes_kernel<3>), grid, dim3(SAT_WQ_NT), stream, p);
+    else SAT_LAUNCH((sat_wgrad7_planes_kernel<9>), grid, dim3(SAT_WQ_NT), stream, p);
+    return sat_check_launch("sat_conv_wgrad7_planes");
+}
+
 // =====================================================================================================================
 // The short-kernel weight gradients: k = 1 convs (one tap) and the K = 2*stride down / up convs (two virtual taps
 // over space-to-depth rows of the longer tensor) — same contract as sat_conv_wgrad (conv_wgrad.hip):

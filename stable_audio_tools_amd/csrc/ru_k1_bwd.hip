@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(512) sat_ru_k1_bwd_kernel(SatRuK1BwdParams p) 
                 out[e] = pre[e] * g.dx;
                 sum_dh[j] += out[e];
             }
-            *reinterpret_cast<f32x4*>(p.dh + ((size_t)b * C + ch) * p.T + t0 + st4) = out;
+            if (p.dh) *reinterpret_cast<f32x4*>(p.dh + ((size_t)b * C + ch) * p.T + t0 + st4) = out;      // (block-uniform; null: only the planes are wanted)
             if (p.em_hi) {
                 uint32_t h0, l0, h1, l1;
                 sat_split2_pk(out[0], out[1], &h0, &l0);
@@ -365,6 +365,8 @@ extern "C" int sat_ru_k1_bwd_nsplit(int B, int C, int T) {
 }
 
 // See the header of this file.  wt_hi / wt_lo: sat_ru_k1_pack(W2).  alpha2 / beta2: snake2's log parameters (C).  dh (B, C, T) out.
+// dh may be NULL when em_hi / em_lo are given: the fp32 store (4 of the kernel's 16 bytes per element) is skipped — for a caller whose
+// consumers of dh both read the planes.
 // em_hi / em_lo (optional): dh as activation planes [B][C/8][em_rows][8], row 32 + t (rows around the sequence stay as the caller
 // zeroed them).  dw_partial [nsplit][C][C] (sum with sat_reduce_splits: torch layout (Cout, Cin, 1)); part [4][C][nsplit] (sum the last
 // axis: d log-alpha2, d log-beta2, bias gradient of the k7 conv = sum dh, bias gradient of the k1 conv = sum dy).
@@ -376,7 +378,8 @@ extern "C" int sat_ru_k1_bwd(const float* dy, const float* h, const short* wt_hi
         sat_set_error("sat_ru_k1_bwd: needs C == 128 and T % 32 == 0 (sat_ru_k1_bwd_nsplit)");
         return 1;
     }
-    if (!dy || !h || !wt_hi || !wt_lo || !alpha2 || !beta2 || !dh || !dw_partial || !part) { sat_set_error("sat_ru_k1_bwd: missing buffer"); return 1; }
+    if (!dy || !h || !wt_hi || !wt_lo || !alpha2 || !beta2 || !dw_partial || !part) { sat_set_error("sat_ru_k1_bwd: missing buffer"); return 1; }
+    if (!dh && !em_hi) { sat_set_error("sat_ru_k1_bwd: dh may only be NULL when its planes are emitted"); return 1; }
     if ((em_hi == nullptr) != (em_lo == nullptr) || (em_hi && em_rows < SAT_RK_LEAD + T)) { sat_set_error("sat_ru_k1_bwd: bad emission planes"); return 1; }
     if ((((uintptr_t)dy | (uintptr_t)h | (uintptr_t)dh | (uintptr_t)em_hi | (uintptr_t)em_lo | (uintptr_t)wt_hi | (uintptr_t)wt_lo) & 15) != 0) {
         sat_set_error("sat_ru_k1_bwd: buffers must be 16-byte aligned");

@@ -313,6 +313,7 @@ SAT_DEVICE float sat_snake(float x, float a, float ib) {
 #if defined(SAT_HIPEMU)
 static inline void sat_glds16(const void* g, void* lds_wave_base) { memcpy((char*)lds_wave_base + 16 * hipemu::lane_id(), g, 16); }
 static inline void sat_glds4(const void* g, void* lds_wave_base) { memcpy((char*)lds_wave_base + 4 * hipemu::lane_id(), g, 4); }
+static inline void sat_glds16_raw(const void* g, void* lds_wave_base) { sat_glds16(g, lds_wave_base); }
 #define SAT_WAIT_VMCNT(n)
 #define SAT_RAW_BARRIER() hipemu::block_barrier()
 #define SAT_WAIT_LGKM0()
@@ -336,6 +337,14 @@ SAT_DEVICE void sat_glds4(const void* g, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
 }
+// The same copy, opaque to the compiler: behind the builtin hipcc treats every later LDS read as a possible reader of the DMA's destination
+// and drains the queue (s_waitcnt vmcnt(0)) in front of it — here the caller orders the copy against its reads itself, with
+// SAT_WAIT_VMCNT and a barrier (conv_wgrad7_planes.h).  lds_wave_base must be wave-uniform (it goes to M0).
+SAT_DEVICE void sat_glds16_raw(const void* g, void* lds_wave_base) {
+    const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base);
+    unsigned keep;                                       // M0 is compiler-reserved and not preserved around a statement: saved and restored inside it
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(g), "s"(m0v) : "memory");
+}
 // counted wait on this wave's LDS-DMA queue + a bare s_barrier: tiles further down the ring stay in flight across the barrier
 // (__syncthreads() would drain them: an LDS-DMA is a pending LDS write on the VM counter)
 #define SAT_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
@@ -347,6 +356,33 @@ SAT_DEVICE void sat_wave_sync() { __builtin_amdgcn_wave_barrier(); }
 // scheduling group: the next `n` instructions of class `mask` (0x8 MFMA, 0x2 VALU, 0x100 DS read, ...) in program order
 #define SAT_SCHED_GROUP(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 SAT_DEVICE bool sat_wave_any(bool v) { return __builtin_amdgcn_ballot_w64(v) != 0; }
+#endif
+
+// Transposed LDS read (ds_read_b64_tr_b16, gfx950): per group of 16 consecutive lanes a block of 4 rows x 16 columns of 16-bit elements
+// comes back column-major.  Lane 4q + p of the group supplies the address of row q, columns 4p .. 4p+3 (8 bytes, 8-byte aligned); lane i
+// receives column i, row q in element q.  The gather crosses lanes: EXEC must be all ones at the read (give every lane an in-bounds
+// address and discard what is not needed — pad, do not mask).  Channel-minor images (conv1d_planes.h) thereby feed time-major MFMA
+// operands (conv_wgrad7_planes.h).
+typedef short bf16x4 __attribute__((ext_vector_type(4)));
+#if defined(SAT_HIPEMU)
+static inline bf16x4 sat_lds_read_tr16_b64(const void* lane_addr) {
+    const void* mine = lane_addr;
+    const char* all = hipemu::wave_exchange(&mine, (int)sizeof(mine));
+    const int l = hipemu::lane_id(), g0 = l & ~15, i = l & 15;
+    bf16x4 r;
+    for (int q = 0; q < 4; ++q) {
+        const char* src;
+        memcpy(&src, all + (size_t)(g0 + 4 * q + (i >> 2)) * hipemu::kSlotBytes, sizeof(src));
+        short v;
+        memcpy(&v, src + 2 * (i & 3), 2);
+        r[q] = v;
+    }
+    return r;
+}
+#else
+SAT_DEVICE bf16x4 sat_lds_read_tr16_b64(const void* lane_addr) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)lane_addr);
+}
 #endif
 
 // s_setprio around the MFMA sections of the generic conv / weight-gradient kernels (conv1d_bf16x3.hip, conv_wgrad*.hip): an A/B switch.

@@ -17,6 +17,7 @@ recompute the worse trade on MI355X.
 """
 import torch
 
+from . import _caches
 from . import ops as _ops_mod
 from .ops import PACK_CONV_DGRAD, PACK_CONV_FWD, PACK_POLYPHASE
 
@@ -151,10 +152,12 @@ def _wn_backward(ops, slabs, saved, g_shape, bias_partial=None):
     return (out[0], out[1].view(g_shape)) + tuple(out[2:])
 
 
-def _conv_fwd(ops, x, w, stride, dil, pad, bias=None, snake=None, res=None, tanh_out=False, dsnake=None, tout=None, cache=None, emit=None):
+def _conv_fwd(ops, x, w, stride, dil, pad, bias=None, snake=None, res=None, tanh_out=False, dsnake=None, tout=None, cache=None, emit=None,
+              keep_planes=None):
     """conv1d(snake(x), w) [+bias] [+res]: the bf16x3 split-MFMA kernel (fp32-accurate, csrc/conv1d_bf16x3.hip) where
     its shape rules allow, else the fp32-MFMA kernel (csrc/conv1d.hip).  cache: DerivedCache of the layer (no-grad / frozen
-    passes only) for the packed planes and the SnakeBeta constants."""
+    passes only) for the packed planes and the SnakeBeta constants.  keep_planes: a dict — a plane-fed k7 conv then reads its planes
+    from the buffer it owns and leaves their handle in keep_planes["kept"] (ops.conv1d_bf16x3); other convs leave it untouched."""
     cout, cin, k = w.shape
     if (res is None and ops.edge_ok(cin, cout, k, stride, dil, pad) and (tout is None or tout == x.shape[2])
             and (snake is None or cout <= 2) and (dsnake is None or cin <= 2) and (emit is None or cin <= 2)):
@@ -165,7 +168,7 @@ def _conv_fwd(ops, x, w, stride, dil, pad, bias=None, snake=None, res=None, tanh
         planes = _cached(cache, "pack_fwd_q" if q else "pack_fwd", (w,), lambda: ops.pack_bf16x3(w, stride=stride, q=q))
         sconsts = _cached(cache, "snake", snake, lambda: ops.snake_consts(snake[0], snake[1])) if snake is not None else None
         return ops.conv1d_bf16x3(x, planes, cout, k, stride, dil, pad, tout=tout, bias=bias,
-                                 snake=snake, res=res, tanh_out=tanh_out, dsnake=dsnake, sconsts=sconsts, emit=emit)
+                                 snake=snake, res=res, tanh_out=tanh_out, dsnake=dsnake, sconsts=sconsts, emit=emit, keep_planes=keep_planes)
     return ops.conv1d(x, _cached(cache, "pack_fwd32", (w,), lambda: ops.pack(w, PACK_CONV_FWD)), cout, k, stride, dil, pad, tout=tout,
                       bias=bias, snake=snake, res=res, tanh_out=tanh_out, dsnake=dsnake)
 
@@ -326,7 +329,11 @@ class ResidualUnitFn(torch.autograd.Function):
             h, y = ops.residual_unit_fwd(x, (a1, b1), w7q, bias1, (a2, b2), w1q, bias2, k1, dil, keep_h=ctx is not None and not recompute and fuse != "nokeep",
                                          emit=emit, sconsts=sc)
         else:
-            h = _conv_fwd(ops, x, w1, 1, dil, pad, bias=bias1, snake=(a1, b1), cache=c1)
+            # a backward will follow: the planes the k7 conv reads stay in its own buffer for the weight gradient (ops.wgrad7_planes)
+            keep = {} if (ops.wgrad7_planes and not recompute and ctx is not None and any(ctx.needs_input_grad)) else None
+            h = _conv_fwd(ops, x, w1, 1, dil, pad, bias=bias1, snake=(a1, b1), cache=c1, keep_planes=keep)
+            if ctx is not None:
+                ctx.k7_planes = keep.get("kept") if keep is not None else None
             y = _conv_fwd(ops, h, w2, 1, 1, 0, bias=bias2, snake=(a2, b2), res=x, cache=c2, emit=emit)
         ctx.ops = ops
         ctx.dil = dil
@@ -353,15 +360,41 @@ class ResidualUnitFn(torch.autograd.Function):
             h = _conv_fwd(ops, x, w1, 1, dil, pad1, bias=bias1, snake=(a1, b1))
         # the k1 data-gradient also writes dh as the planes its consumer — the k7 data-gradient two launches below — reads
         want_emit = ops.emit_ok(w1.shape[0], k2, 1, t, dil) and ops.k7q_applicable(w1.shape[0], k1, 1, dil, pad1, c)
+        # the k7 weight gradient from planes (csrc/conv_wgrad7_planes.h): dh's, emitted below, and the ones the forward conv read — if they
+        # are still what it read (same x, same parameters, the owned buffer not rewritten since); anything else keeps the fp32 kernel
+        kp = getattr(ctx, "k7_planes", None)
+        bsz = dy.shape[0]
+        skip_dh = False
+        if kp is not None and not (ops.wgrad7_planes and not ctx.recompute and want_emit and k1 == 7 and w1.shape[0] == c
+                                   and kp["gen"] == kp["buf"]["gen"] and kp["ptr"] == x.data_ptr() and kp["shape"] == tuple(x.shape)
+                                   and kp["ver"] == _caches.version_of(x) and kp["snake"] == ops._snake_key((a1, b1))
+                                   and ops.conv_wgrad7_planes_ok(bsz, c, c, t, dil, pad1, kp["buf"]["rows"], kp["buf"]["rows"])):
+            kp = None
+
+        def wgrad1(dh, bias_grad):
+            em = ops._peek_emitted(dh, None) if kp is not None else None
+            if em is None or not ops.conv_wgrad7_planes_ok(bsz, c, c, t, dil, pad1, em["rows"], kp["buf"]["rows"]):
+                return _conv_wgrad(ops, dh, x, k1, 1, dil, pad1, (a1, b1), bias_grad=bias_grad, raw=bool(wn1))
+            dw = ops.conv_wgrad7_planes((em["hi"], em["lo"], em["rows"]), (kp["buf"]["hi"], kp["buf"]["lo"], kp["buf"]["rows"]),
+                                        bsz, c, c, t, dil, pad1, raw=bool(wn1))
+            return (dw, ops.rowsum(dh, partial=bool(wn1))) if bias_grad else dw
         if k2 == 1 and w2.shape[0] == c and w1.shape[0] == c and ops.ru_k1_bwd_ok(dy.shape[0], c, t):
             # C == 128 (the widest levels): weight gradient, data gradient, both bias gradients and the snake gradients of the 1x1 conv in ONE pass
             # over dy and h (csrc/ru_k1_bwd.hip) instead of three kernels that each stream them from HBM
-            dh, da2, db2, dw2, dbias2, dbias1 = ops.ru_k1_bwd(dy, h, w2, (a2, b2), emit=want_emit, raw=bool(wn2))
-            dw1 = _conv_wgrad(ops, dh, x, k1, 1, dil, pad1, (a1, b1), bias_grad=False, raw=bool(wn1))
+            # (both consumers of dh read its planes: the kernel then does not store fp32 dh at all)
+            skip_dh = bool(kp is not None and ops.ru_k1_bwd_skip_dh)
+            dh, da2, db2, dw2, dbias2, dbias1 = ops.ru_k1_bwd(dy, h, w2, (a2, b2), emit=want_emit, raw=bool(wn2), skip_dh=skip_dh)
+            # (a skipped dh is marked in ops until this backward ends: every fp32 reader of it raises instead of reading garbage)
+            try:
+                dw1 = wgrad1(dh, False)
+                if skip_dh:
+                    dx, da1, db1 = _conv_dgrad(ops, dh, w1, k1, 1, dil, pad1, c, t, (x, a1, b1), res=dy)
+            finally:
+                ops.dh_written()
         else:
             dw2, dbias2 = ops.conv_wgrad(dy, h, k2, 1, 1, 0, snake=(a2, b2), snake_on=2, lo_rowsum=True, raw=bool(wn2))
             dh, da2, db2 = _conv_dgrad(ops, dy, w2, k2, 1, 1, 0, c, t, (h, a2, b2), emit={"snake": None} if want_emit else None)
-            dw1, dbias1 = _conv_wgrad(ops, dh, x, k1, 1, dil, pad1, (a1, b1), bias_grad=True, raw=bool(wn1))
+            dw1, dbias1 = wgrad1(dh, True)
         dg1 = dg2 = None
         if wn1:         # a raw weight gradient brings its bias gradient as per-split sums (C, R): finished in the same launch
             if dbias1.dim() == 2:
@@ -373,7 +406,8 @@ class ResidualUnitFn(torch.autograd.Function):
                 dw2, dg2, dbias2 = _wn_backward(ops, dw2, wn2, gs2, bias_partial=dbias2)
             else:
                 dw2, dg2 = _wn_backward(ops, dw2, wn2, gs2)
-        dx, da1, db1 = _conv_dgrad(ops, dh, w1, k1, 1, dil, pad1, c, t, (x, a1, b1), res=dy)
+        if not skip_dh:
+            dx, da1, db1 = _conv_dgrad(ops, dh, w1, k1, 1, dil, pad1, c, t, (x, a1, b1), res=dy)
         return dx, da1, db1, dw1, dbias1, da2, db2, dw2, dbias2, None, None, None, None, None, None, dg1, dg2
 
 

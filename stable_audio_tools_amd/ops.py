@@ -209,7 +209,7 @@ class SatOps:
             if esnake is not None:
                 ela, elb = esnake
                 self._f32(ela, elb)
-            ehi, elo, erows = self._emit_planes(b, cout, t, x.device, self._stream(x))
+            ehi, elo, erows = self._emit_planes(b, cout, t, x.device, self._stream(x), owner=esnake)
         self._chk(self.lib.sat_edge_conv(_ptr(x), _ptr(w), _ptr(bias), _ptr(alpha), _ptr(beta), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2),
                                          _ptr(pda), _ptr(pdb), _ptr(ehi), _ptr(elo), _ptr(ela), _ptr(elb), erows, b, cin, cout, t, k, pad, mode,
                                          int(tanh_out), self._stream(x)))
@@ -325,7 +325,7 @@ class SatOps:
             ea = eib = None
             if esnake is not None:
                 ea, eib = self.snake_consts(esnake[0], esnake[1])
-            ehi, elo, erows = self._emit_planes(b, cout, tout, x.device, self._stream(x))
+            ehi, elo, erows = self._emit_planes(b, cout, tout, x.device, self._stream(x), owner=esnake)
             self._chk(self.lib.sat_conv1d_bf16x3_emit(_ptr(x), _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(sa), _ptr(sib),
                                                       _ptr(res), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb),
                                                       b, cin, cout, tin, tout, *dims, int(tanh_out), _ptr(ehi), _ptr(elo), _ptr(ea), _ptr(eib),
@@ -433,10 +433,55 @@ class SatOps:
         return (self.k7_emit and self.use_bf16x3 and cin <= 2 and self.edge_ok(cin, cout, k, stride, dil, pad)
                 and self.k7q_applicable(cout, 7, 1, consumer_dil, 3 * consumer_dil, cout))
 
-    def _emit_planes(self, b, c, t, device, st, alt=False):
+    # ---- the k7 weight gradient from planes (csrc/conv_wgrad7_planes.h) ----
+    wgrad7_planes = True    # the ResidualUnits' k7 weight gradient reads dh's emitted planes and the planes its forward conv read (kept in a buffer
+                            # owned by that conv, 4 bytes per element of every k7 input: +12.3 GB per batch item) instead of re-loading fp32,
+                            # re-evaluating SnakeBeta and re-splitting in the kernel.  False: the pipelined kernel and the shared per-shape plane
+                            # buffers, as before (A/B: bench.py --ops-set wgrad7_planes=0; figures: profiles/wgrad7_planes/README.md)
+                            # Measured peak_hbm_gib of the real step: batch 1 49.5 -> 60.97, batch 4 184.0 -> 199.86 (with the budget below; without it
+                            # 229.8, where the 288 GB card's allocator thrashes and the step is 2.6x slower).  The buffers are keyed by the parameters'
+                            # storage and never evicted: a rebuilt or reloaded model, an eval copy or another input length pins another set until
+                            # release_owned_planes() / release_workspaces()
+    wgrad7_planes_budget_gib = 16.0     # most that all owned plane buffers together may hold: the flagship step (batch 1) needs 11.5 GiB; convs that
+                                        # come after the budget is spent keep the fp32 weight gradient
+    ru_k1_bwd_skip_dh = True    # sat_ru_k1_bwd does not store fp32 dh when both of dh's consumers (k7 weight gradient, k7q data-gradient) read
+                                # its planes: 4 of the kernel's 16 bytes per element (A/B: bench.py --ops-set ru_k1_bwd_skip_dh=0)
+
+    def _owned_planes(self, snake, b, c, t, device, st, create=False):
+        """The plane buffer owned by the k7 conv whose SnakeBeta parameters are `snake` (keyed by their storage, shape and device; used from the stream that created it):
+        what that conv reads in its forward stays valid until its backward, and its address is the same every step (HIP-graph replay).
+        Zero-filled once; never created while the stream is capturing (None: the caller takes the shared buffers)."""
+        if snake is None or not self.wgrad7_planes:
+            return None
+        key = (snake[0].data_ptr(), snake[1].data_ptr(), b, c, t, device)
+        cache = self.__dict__.setdefault("_own_planes", {})
+        own = cache.get(key)
+        capturing = device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        sv = st.value if st is not None else 0
+        # one stream per buffer — except a capture (its own stream, whatever the caller's): the graph is replayed on the caller's stream,
+        # in order with the eager steps that created the buffer
+        if own is not None and own["stream"] != sv and not capturing:
+            return None
+        if own is None and create:
+            if capturing:
+                return None
+            rows = self.lib.sat_conv1d_k7_plane_rows(t, t, 0)
+            n = b * ((c + 7) // 8) * rows * 8
+            held = sum(4 * o["hi"].numel() for o in cache.values())
+            if held + 4 * n > self.wgrad7_planes_budget_gib * 2 ** 30:
+                return None                                       # over the budget: this conv keeps the shared buffers and the fp32 weight gradient
+            own = {"hi": _keep_zeros(n, torch.int16, device), "lo": _keep_zeros(n, torch.int16, device), "rows": rows, "gen": 0, "stream": sv}
+            cache[key] = own
+        return own
+
+    def _emit_planes(self, b, c, t, device, st, alt=False, owner=None):
         """Emission target for a (b, c, t) tensor: planes [b][ceil(c/8)][rows][8] with the rows around the sequence zero.  One pair
         per (shape, device, stream) (+ an alternate for the fused unit, which reads one while writing the other), zero-filled ONCE:
         producers only ever write rows 32 .. 32 + t - 1 of existing channels."""
+        own = self._owned_planes(owner, b, c, t, device, st)        # the consumer keeps its planes for its backward (wgrad7_planes)
+        if own is not None:
+            own["gen"] += 1
+            return own["hi"], own["lo"], own["rows"]
         rows = self.lib.sat_conv1d_k7_plane_rows(t, t, 0)          # pad 0 needs the most rows: valid for every consumer padding
         key = ("emit", b, c, t, device, st.value if st is not None else 0, alt)
         cache = self.__dict__.setdefault("_planes", {})
@@ -458,10 +503,19 @@ class SatOps:
             return e
         return None
 
+    def _peek_emitted(self, x, snake):
+        """_take_emitted without consuming: the planes stay for the conv that takes them next."""
+        e = self.__dict__.get("_emitted")
+        if (e is not None and e["ptr"] == x.data_ptr() and e["shape"] == tuple(x.shape) and _caches.trackable(x)
+                and e["ver"] == _caches.version_of(x) and e["snake"] == self._snake_key(snake)):
+            return e
+        return None
+
     def conv1d_bf16x3(self, x, w_planes, cout, k, stride=1, dil=1, pad=0, tout=None, bias=None, snake=None, res=None,
-                      tanh_out=False, dsnake=None, out=None, sconsts=None, emit=None):
+                      tanh_out=False, dsnake=None, out=None, sconsts=None, emit=None, keep_planes=None):
         """Same contract as conv1d; `snake` = (log-alpha, log-beta) as everywhere else; sconsts = snake_consts(*snake) if the
-        caller keeps them (frozen layers)."""
+        caller keeps them (frozen layers).  keep_planes (a dict, q-packed k7 convs only): a backward will follow — the planes are read from
+        the buffer this conv owns (_owned_planes) and keep_planes["kept"] tells the backward where they are and what makes them stale."""
         b, cin, tin = x.shape
         if tout is None:
             tout = (tin + 2 * pad - dil * (k - 1) - 1) // stride + 1
@@ -469,7 +523,7 @@ class SatOps:
         if len(w_planes) == 3:          # sat_pack_weights_k7q layout (pack_bf16x3(q=True) after k7q_applicable)
             if not (stride == 1 and 5 <= k <= 7 and 0 <= pad <= 32 and (k - 1) * dil <= 62):
                 raise ValueError("conv1d_bf16x3: q-packed weights need stride 1, 5 <= K <= 7, pad <= 32, (K-1)*dil <= 62")
-            return self._k7_planes_call(rows, x, w_planes, cout, tout, k, dil, pad, bias, snake, res, tanh_out, dsnake, out, sconsts)
+            return self._k7_planes_call(rows, x, w_planes, cout, tout, k, dil, pad, bias, snake, res, tanh_out, dsnake, out, sconsts, keep_planes)
         return self._bf16x3_call(self.lib.sat_conv1d_bf16x3, rows, x, w_planes, cout, tout, (k, stride, dil, pad),
                                  bias, snake, res, tanh_out, dsnake, out, sconsts, emit)
 
@@ -477,7 +531,8 @@ class SatOps:
     # (plane emission) or by one conversion pass per conv (sat_conv1d_k7_planes) instead of one per workgroup.  The two planes live in
     # a cached workspace of the largest size seen, one per (device, stream): the pre-pass and its conv are enqueued back to back on
     # the caller's current stream.
-    def _k7_planes_call(self, prows, x, w_planes, cout, tout, k, dil, pad, bias, snake, res, tanh_out, dsnake, out=None, sconsts=None):
+    def _k7_planes_call(self, prows, x, w_planes, cout, tout, k, dil, pad, bias, snake, res, tanh_out, dsnake, out=None, sconsts=None,
+                        keep_planes=None):
         b, cin, tin = x.shape
         self._f32(x, bias, res)
         sa = sib = None
@@ -485,8 +540,24 @@ class SatOps:
             sa, sib = sconsts if sconsts is not None else self.snake_consts(snake[0], snake[1])
         st = self._stream(x)
         em = self._take_emitted(x, snake)
+        # keep_planes (ResidualUnitFn.forward, when a backward will follow): the planes live in the buffer this conv owns, and the
+        # handle says what makes them stale: a rewrite of the buffer, another x, edited parameters
+        keep = keep_planes is not None
+        if em is None:
+            self._check_written(x)
+        own = self._owned_planes(snake, b, cin, tin, x.device, st, create=True) if keep and tin == tout and _caches.trackable(x) else None
+        if own is not None and em is None:
+            hi, lo, rows = own["hi"], own["lo"], own["rows"]
+            own["gen"] += 1
+            self._chk(self.lib.sat_conv1d_k7_planes(_ptr(x), _ptr(sa), _ptr(sib), _ptr(hi), _ptr(lo), b, cin, tin, rows, st))
+        if own is not None and (em is None or em["hi"].data_ptr() == own["hi"].data_ptr()):
+            # (emitted into a shared buffer — the first step, before this conv owned one: the backward keeps the fp32 path this once)
+            keep_planes["kept"] = {"buf": own, "gen": own["gen"], "ptr": x.data_ptr(), "shape": tuple(x.shape), "ver": _caches.version_of(x),
+                             "snake": self._snake_key(snake)}
         if em is not None:
             hi, lo, rows = em["hi"], em["lo"], em["rows"]          # the producer's epilogue already wrote act(x) as planes
+        elif own is not None:
+            pass
         else:
             rows = self.lib.sat_conv1d_k7_plane_rows(tin, tout, pad)
             c8 = (cin + 7) // 8
@@ -595,10 +666,11 @@ class SatOps:
         self._chk(self.lib.sat_ru_k1_pack(_ptr(w2), _ptr(planes[0]), _ptr(planes[1]), c, self._stream(w2)))
         return planes[0], planes[1]
 
-    def ru_k1_bwd(self, dy, h, w2, snake2, emit=False, wt=None, raw=False):
+    def ru_k1_bwd(self, dy, h, w2, snake2, emit=False, wt=None, raw=False, skip_dh=False):
         """Backward of y = x + conv1x1(snake2(h)) w.r.t. everything but x, in one launch: returns (dh, dlog_alpha2, dlog_beta2, dW2 (C, C, 1),
         dbias2 (C,), dbias1 (C,) = sum dh).  emit=True also writes dh as the activation planes of the k7 data-gradient that consumes it
-        next (as conv1d_bf16x3(emit={"snake": None})).  raw=True: dW2 as WgradSlabs (for wn_grad_splits)."""
+        next (as conv1d_bf16x3(emit={"snake": None})).  raw=True: dW2 as WgradSlabs (for wn_grad_splits).  skip_dh (needs emit): the returned
+        dh is allocated but NOT written — only its planes are; for a caller whose consumers of dh all read the planes."""
         b, c, t = dy.shape
         a2, b2 = snake2
         self._f32(dy, h, w2, a2, b2)
@@ -614,10 +686,15 @@ class SatOps:
         erows = 0
         if emit:
             ehi, elo, erows = self._emit_planes(b, c, t, dy.device, st)
-        self._chk(self.lib.sat_ru_k1_bwd(_ptr(dy), _ptr(h), _ptr(wt_hi), _ptr(wt_lo), _ptr(a2), _ptr(b2), _ptr(dh), _ptr(ehi), _ptr(elo), erows,
-                                         _ptr(slabs), _ptr(part), b, c, t, st))
+        if skip_dh and not emit:
+            raise ValueError("ru_k1_bwd: skip_dh needs emit=True")
+        self._dh_unwritten = dh.data_ptr() if skip_dh else None
+        self._chk(self.lib.sat_ru_k1_bwd(_ptr(dy), _ptr(h), _ptr(wt_hi), _ptr(wt_lo), _ptr(a2), _ptr(b2), None if skip_dh else _ptr(dh),
+                                         _ptr(ehi), _ptr(elo), erows, _ptr(slabs), _ptr(part), b, c, t, st))
         if emit:
             self._note_emitted(dh, None, ehi, elo, erows)
+            if skip_dh and self._emitted is None:
+                raise RuntimeError("ru_k1_bwd: dh was skipped but its planes cannot be tracked")
         dw2 = WgradSlabs(slabs, ns, (c, c, 1), (c, 1, 1))
         if not raw:
             dw2 = dw2.reduce(self)
@@ -635,6 +712,7 @@ class SatOps:
         n = x.shape[1]
         alpha, beta = snake if snake is not None else (None, None)
         self._f32(dy, x, alpha, beta)
+        self._check_written(dy)
         nsplit = self.lib.sat_conv_wgrad7_bf16x3_nsplit(b, m, n, t)
         partial = torch.empty(nsplit, m * n * 7, dtype=torch.float32, device=dy.device)
         # slabs are written tap-major ([7][M][N]: the 32 lanes of an accumulator row store 128 contiguous bytes; the
@@ -651,11 +729,43 @@ class SatOps:
             return dw, (rs if fused else self.rowsum(dy, partial=True))
         return dw, (self._sum_last(rs) if fused else self.rowsum(dy))
 
+    def _check_written(self, t):
+        """A dh whose fp32 store ru_k1_bwd(skip_dh=True) skipped exists only as planes: reading it as fp32 is a bug, not a fallback."""
+        if t is not None and self.__dict__.get("_dh_unwritten") is not None and t.data_ptr() == self._dh_unwritten:
+            raise RuntimeError("this tensor is a dh that sat_ru_k1_bwd did not write (skip_dh): only its planes exist")
+
+    def dh_written(self):
+        """The backward that skipped a dh store is over: its address means nothing any more."""
+        self._dh_unwritten = None
+
+    def release_owned_planes(self):
+        """Drop every plane buffer a k7 conv owns (wgrad7_planes): after a model is discarded or reloaded, or before a pass at another
+        input length.  The next training step re-creates what it needs (its first backward takes the fp32 weight-gradient kernel where
+        the planes were emitted before the buffer existed).  Not while a captured graph that uses them may still be replayed."""
+        self.__dict__.pop("_own_planes", None)
+
+    def conv_wgrad7_planes_ok(self, b, m, n, t, dil, pad, rows_dy, rows_act):
+        return self.use_bf16x3 and self.wgrad7_planes and self.lib.sat_conv_wgrad7_planes_ok(b, m, n, t, dil, pad, rows_dy, rows_act) == 1
+
+    def conv_wgrad7_planes(self, dy_planes, act_planes, b, m, n, t, dil, pad, raw=False):
+        """dW (Cout, Cin, 7) as conv_wgrad7_bf16x3, both operands as (hi, lo, rows) planes: dy's and act(x)'s (sat_conv1d_k7_planes layout)."""
+        dhi, dlo, drows = dy_planes
+        ahi, alo, arows = act_planes
+        if self.lib.sat_conv_wgrad7_planes_ok(b, m, n, t, dil, pad, drows, arows) != 1:
+            raise RuntimeError("conv_wgrad7_planes: shape not served by the planes kernel (conv_wgrad7_planes_ok)")
+        nsplit = self.lib.sat_conv_wgrad7_planes_nsplit(b, m, n, t)
+        partial = torch.empty(nsplit, m * n * 7, dtype=torch.float32, device=dhi.device)
+        self._chk(self.lib.sat_conv_wgrad7_planes(_ptr(dhi), _ptr(dlo), drows, _ptr(ahi), _ptr(alo), arows, _ptr(partial), n, 1, m * n,
+                                                  b, m, n, t, dil, pad, self._stream(dhi)))
+        slabs = WgradSlabs(partial, nsplit, (m, n, 7), (n, 1, m * n))       # tap-major, as conv_wgrad7_bf16x3
+        return slabs if raw else slabs.reduce(self)
+
     def rowsum(self, x, partial=False):
         """(B, C, T) -> (C,) sum over batch and time: per-(channel, time split) partial sums laid out [C][nsplit], summed
         by a second pass of the same kernel (deterministic, no atomics).  partial=True: the first pass only, (C, nsplit) — for a
         consumer that finishes the sum itself (wn_grad_splits)."""
         self._f32(x)
+        self._check_written(x)
         b, c, t = x.shape
         while True:
             ns = self.lib.sat_rowsum_nsplit(t)
@@ -762,7 +872,7 @@ class SatOps:
     def release_workspaces(self):
         """Drop the cached plane / emission buffers (they are per activation shape and re-created, zero-filled, on demand): call after a
         run at a batch size or length that will not come back, before torch.cuda.empty_cache()."""
-        for name in ("_planes", "_disc_pool", "_disc_gen", "_disc_geoms"):
+        for name in ("_planes", "_own_planes", "_disc_pool", "_disc_gen", "_disc_geoms"):
             d = self.__dict__.get(name)
             if d is not None:
                 d.clear()
