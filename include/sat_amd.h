@@ -430,6 +430,23 @@ int sat_rope_tables(const float* inv_freq, float* cs, int N, int half, float pos
 int sat_rope_apply(void* t, const float* cs, long long sb, long long sn, long long sh, int B, int N, int H, int half,
                    int tab_off, int transpose, int dtype, void* stream);
 
+/* q / k head normalisation of Attention(qk_norm="ln" | "l2") (transformer.py:374-376, :397-403, :485-489) with the rotary that follows it,
+ * one pass (training and fp32 paths; the no-grad bf16 path has it in sat_gemm_qkv_norm_bf16).  Element d of head j of token t sits at
+ * t * stride + j * 64 + d (xs / ys: token strides in elements); the first nh heads of every token are normalised, heads j < hq with the
+ * q tables, the others with the k tables ((64) fp32, 16-byte aligned, NULL for "l2").  mode 1 = "ln" (eps, biased variance), 2 = "l2".
+ * cs: (tab_off + ntok, 16, 2) rotary table or NULL; tokens = batch * ntok.  stat fp32 or NULL: "ln" (2, tokens * nh) = mean | rstd,
+ * "l2" (tokens * nh) = 1 / max(||x||, 1e-12).  Rows must be 16-byte (fp32) / 8-byte (bf16) aligned. */
+int sat_qk_norm_fwd(const void* x, long long xs, void* y, long long ys, const float* q_gamma, const float* q_beta,
+                    const float* k_gamma, const float* k_beta, const float* cs, int tab_off, float* stat, int tokens, int ntok,
+                    int nh, int hq, int mode, float eps, int dtype, void* stream);
+/* Backward: dy (gradient of y, same layout) is replaced IN PLACE by the gradient of x — inverse rotary, then the norm's backward with
+ * x-hat recomputed from the raw x and stat.  "ln": part (sat_qk_norm_bwd_nblocks(tokens * nh), 2, 2, 64) fp32 receives per-block sums
+ * [q | k][dgamma | dbeta] (reduce with sat_reduce_splits). */
+int sat_qk_norm_bwd_nblocks(long long rows);
+int sat_qk_norm_bwd(void* dy, long long ys, const void* x, long long xs, const float* q_gamma, const float* k_gamma,
+                    const float* cs, int tab_off, const float* stat, float* part, int tokens, int ntok, int nh, int hq,
+                    int mode, int dtype, void* stream);
+
 /* GLU.forward (transformer.py:274-275): out = x * silu(gate) for xin = [x | gate] (rows, 2F);
  * backward != 0: out = d_xin (rows, 2F) from dout (rows, F). */
 int sat_swiglu(const void* xin, const void* dout, void* out, long long rows, int F, int backward, int dtype,
@@ -498,6 +515,14 @@ int sat_gemm_bf16(const void* A, long long lda, const void* B, long long ldb, vo
 int sat_gemm_qkv_bf16(const void* A, long long lda, const void* B, long long ldb, const float* rope_cs, int rope_off,
                       void* q_rm, void* k_rm, void* v_tr, const void* zeros, int nb, int ntok, int npad, int heads,
                       int K, int sec0, int nsec, int tile, void* stream);
+/* The same with Attention(qk_norm=...) (transformer.py:374-376, :485-489) in the epilogue: every q / k head row is normalised after the
+ * projection and before the rotary, v is untouched.  mode 1 = "ln": LayerNorm over the 64 head dims (fp32 statistics, biased variance,
+ * eps) with the (64) fp32 tables q_gamma / q_beta for q heads and k_gamma / k_beta for k heads (16-byte aligned; a table pair whose
+ * section is not produced may be NULL); mode 2 = "l2": x / max(||x||_2, 1e-12), tables NULL.  tile: 0, 7 or 8 (no 256 x 256 norm epilogue). */
+int sat_gemm_qkv_norm_bf16(const void* A, long long lda, const void* B, long long ldb, const float* rope_cs, int rope_off,
+                           void* q_rm, void* k_rm, void* v_tr, const void* zeros, int nb, int ntok, int npad, int heads,
+                           int K, int sec0, int nsec, int tile, int mode, const float* q_gamma, const float* q_beta,
+                           const float* k_gamma, const float* k_beta, float eps, void* stream);
 
 /* Second half of a split-K projection (sat_gemm_bf16 with splits > 1 writes fp32 slabs): out = sum_z slabs[z] (+ bias) (+ res),
  * in bf16 or fp32 — used for the few-tile / long-K projections (FF2), where cutting K doubles the workgroups on the chip. */

@@ -115,6 +115,7 @@ SIGNATURES = {
     # gemm.hip
     "sat_gemm_bf16": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _L, _I, _P, _L, _P] + [_I] * 7 + [_P]),
     "sat_gemm_qkv_bf16": (_I, [_P, _L, _P, _L, _P, _I, _P, _P, _P, _P] + [_I] * 8 + [_P]),
+    "sat_gemm_qkv_norm_bf16": (_I, [_P, _L, _P, _L, _P, _I, _P, _P, _P, _P] + [_I] * 9 + [_P] * 4 + [_F, _P]),
     "sat_gemm_fp8": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _L, _I, _P, _L, _P, _P, _P, _P] + [_I] * 6 + [_P]),
     "sat_gemm_qkv_fp8": (_I, [_P, _L, _P, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P] + [_I] * 8 + [_P]),
     "sat_quant_fp8": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _P]),
@@ -134,6 +135,9 @@ SIGNATURES = {
     "sat_layernorm_bwd_res": (_I, [_P] * 5 + [_L] + [_P] * 5 + [_I] * 4 + [_P]),
     "sat_rope_tables": (_I, [_P, _P, _I, _I, _F, _P]),
     "sat_rope_apply": (_I, [_P, _P, _L, _L, _L] + [_I] * 7 + [_P]),
+    "sat_qk_norm_fwd": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _P] + [_I] * 5 + [_F, _I, _P]),
+    "sat_qk_norm_bwd_nblocks": (_I, [_L]),
+    "sat_qk_norm_bwd": (_I, [_P, _L, _P, _L, _P, _P, _P, _I, _P, _P] + [_I] * 6 + [_P]),
     "sat_swiglu": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
     "sat_gate_residual": (_I, [_P, _P, _L, _P, _P, _I, _I, _I, _I, _P]),
     "sat_gate_residual_bwd_nchunks": (_I, [_I]),

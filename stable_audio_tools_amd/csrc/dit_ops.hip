@@ -602,6 +602,222 @@ extern "C" int sat_rope_apply(void* t, const float* cs, long long sb, long long 
 }
 
 // ------------------------------------------------------------------------------------------------
+// q / k head normalisation of Attention(qk_norm="ln" | "l2") (transformer.py:374-376, :397-403, :485-489), with the rotary that follows
+// it in the same pass — the training and fp32 paths (the no-grad bf16 path has it in the projection GEMM's epilogue, gemm.hip).
+// A "row" is one (token, head) vector of 64 values: element d of head j of token t sits at t * stride + j * 64 + d, heads 0 .. nh-1 are
+// normalised (the q and k heads of a fused (B, N, 3*H*64) projection: nh = 2H; q alone: nh = H; the k half of (B, M, 2*Hkv*64): nh = Hkv),
+// heads j < hq take the q tables, the others the k tables.  16 lanes per row, 4 columns per lane (16-byte fp32 / 8-byte bf16 accesses),
+// the row statistics are 16-lane butterflies.  mode 1 = "ln" (fp32 mean / biased variance, eps, affine), 2 = "l2" (x / max(|x|, 1e-12)).
+// ------------------------------------------------------------------------------------------------
+struct SatQkNormParams {
+    const void* x;        // raw projection
+    void* y;              // forward: normalised (+ rotated) rows
+    void* dy;             // backward: gradient of y, replaced IN PLACE by the gradient of x
+    const float* gq;      // (64) fp32 tables, null for "l2"
+    const float* bq;
+    const float* gk;
+    const float* bk;
+    const float* cs;      // (Ntab, 16, 2) rotary cos / sin or null
+    float* stat;          // "ln": (2, rows) mean | rstd; "l2": (rows) 1 / max(|x|, 1e-12)
+    float* part;          // backward, "ln": (nblocks, 2, 2, 64) per-block sums [q | k][dgamma | dbeta]
+    long long xs, ys;     // token strides (elements) of x and of y / dy
+    long long rows;       // tokens * nh
+    int ntok, nh, hq, tab_off, mode, iters;
+    float eps;
+};
+
+template <typename T> struct SatRow4;
+template <> struct SatRow4<float> {
+    static SAT_DEVICE f32x4 ld(const void* p, long long i) { return *reinterpret_cast<const f32x4*>((const float*)p + i); }
+    static SAT_DEVICE void st(void* p, long long i, f32x4 v) { *reinterpret_cast<f32x4*>((float*)p + i) = v; }
+};
+template <> struct SatRow4<short> {
+    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+    static SAT_DEVICE f32x4 ld(const void* p, long long i) {
+        const u32x2_t u = *reinterpret_cast<const u32x2_t*>((const short*)p + i);
+        f32x4 v;
+        v[0] = __builtin_bit_cast(float, u[0] << 16);
+        v[1] = __builtin_bit_cast(float, u[0] & 0xffff0000u);
+        v[2] = __builtin_bit_cast(float, u[1] << 16);
+        v[3] = __builtin_bit_cast(float, u[1] & 0xffff0000u);
+        return v;
+    }
+    static SAT_DEVICE void st(void* p, long long i, f32x4 v) {
+        u32x2_t u;
+        u[0] = sat_cvt2_pk(v[0], v[1]);
+        u[1] = sat_cvt2_pk(v[2], v[3]);
+        *reinterpret_cast<u32x2_t*>((short*)p + i) = u;
+    }
+};
+SAT_DEVICE float sat_group16_sum(float v) {
+    for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+// partial rotary on the lane's four columns c .. c+3 (first 32 dims, NeoX pairs (d, d + 16)); pv = the partner columns c ^ 16, which
+// live 4 lanes away in the row's 16-lane group.  sign +1: forward, -1: transpose (backward).
+SAT_DEVICE f32x4 sat_qk_rotate(f32x4 v, f32x4 pv, const float* cs, long long tab_row, int c, float sign) {
+    const float* t = cs + (tab_row * 16 + (c & 15)) * 2;
+    const f32x4 cs0 = *reinterpret_cast<const f32x4*>(t), cs1 = *reinterpret_cast<const f32x4*>(t + 4);
+    const float co[4] = {cs0[0], cs0[2], cs1[0], cs1[2]}, si[4] = {cs0[1], cs0[3], cs1[1], cs1[3]};
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (c < 16) ? v[e] * co[e] - pv[e] * (sign * si[e]) : v[e] * co[e] + pv[e] * (sign * si[e]);
+    return o;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) sat_qk_norm_fwd_kernel(SatQkNormParams p) {
+    const int c = (threadIdx.x & 15) * 4;
+    const long long row = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (row >= p.rows) return;            // a whole 16-lane group leaves together: the butterflies below stay inside a group
+    const long long tok = row / p.nh;
+    const int j = (int)(row - tok * p.nh);
+    f32x4 v = SatRow4<T>::ld(p.x, tok * p.xs + j * 64 + c);
+    float mean = 0.f, rs;
+    if (p.mode == 1) {
+        mean = sat_group16_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
+        v -= mean;
+    }
+    const float ss = sat_group16_sum((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
+    rs = (p.mode == 1) ? 1.0f / sqrtf(ss * (1.0f / 64.0f) + p.eps) : 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+    v *= rs;
+    if (p.mode == 1) {
+        const float* g = j < p.hq ? p.gq : p.gk;
+        const float* b = j < p.hq ? p.bq : p.bk;
+        v = v * *reinterpret_cast<const f32x4*>(g + c) + *reinterpret_cast<const f32x4*>(b + c);
+    }
+    if (p.cs) {
+        f32x4 pv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pv[e] = __shfl_xor(v[e], 4);
+        if (c < 32) v = sat_qk_rotate(v, pv, p.cs, p.tab_off + tok % p.ntok, c, 1.0f);
+    }
+    SatRow4<T>::st(p.y, tok * p.ys + j * 64 + c, v);
+    if (p.stat && c == 0) {
+        p.stat[row] = (p.mode == 1) ? mean : rs;
+        if (p.mode == 1) p.stat[p.rows + row] = rs;
+    }
+}
+
+// Backward, one pass over dy: inverse rotary, then the norm's backward, written over dy.  x-hat comes from the saved raw projection and
+// the saved statistics (never from y / gamma: a gamma may be zero or negative).  "ln" also accumulates dgamma = sum dy * x-hat and
+// dbeta = sum dy over the block's rows (p.iters sweeps of 16 rows), one (2, 2, 64) slab per block for sat_reduce_splits.
+template <typename T>
+__global__ void __launch_bounds__(256) sat_qk_norm_bwd_kernel(SatQkNormParams p) {
+    __shared__ float red[4][4][64];         // [wave][q dgamma | q dbeta | k dgamma | k dbeta][column]
+    const int c = (threadIdx.x & 15) * 4, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    f32x4 acc[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < p.iters; ++it) {
+        const long long row = ((long long)blockIdx.x * p.iters + it) * 16 + (threadIdx.x >> 4);
+        const bool ok = row < p.rows;       // (predicated, not skipped: every lane takes part in the shuffles; a row past the end re-reads the
+                                            // last row, which its owner may be overwriting — that value is never stored or accumulated)
+        const long long rc = ok ? row : p.rows - 1;
+        const long long tok = rc / p.nh;
+        const int j = (int)(rc - tok * p.nh);
+        f32x4 g = SatRow4<T>::ld(p.dy, tok * p.ys + j * 64 + c);
+        if (p.cs) {
+            f32x4 pg;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pg[e] = __shfl_xor(g[e], 4);
+            if (c < 32) g = sat_qk_rotate(g, pg, p.cs, p.tab_off + tok % p.ntok, c, -1.0f);
+        }
+        f32x4 xh = SatRow4<T>::ld(p.x, tok * p.xs + j * 64 + c);
+        f32x4 dx;
+        if (p.mode == 1) {
+            const bool isq = j < p.hq;
+            xh = (xh - p.stat[rc]) * p.stat[p.rows + rc];
+            const float rs = p.stat[p.rows + rc];
+            if (ok) {
+                if (isq) { acc[0] += g * xh; acc[1] += g; }
+                else { acc[2] += g * xh; acc[3] += g; }
+            }
+            g *= *reinterpret_cast<const f32x4*>((isq ? p.gq : p.gk) + c);
+            const float s1 = sat_group16_sum((g[0] + g[1]) + (g[2] + g[3])) * (1.0f / 64.0f);
+            const float s2 = sat_group16_sum((g[0] * xh[0] + g[1] * xh[1]) + (g[2] * xh[2] + g[3] * xh[3])) * (1.0f / 64.0f);
+            dx = (g - s1 - xh * s2) * rs;
+        } else {
+            const float inv = p.stat[rc];
+            xh *= inv;
+            const float s2 = sat_group16_sum((g[0] * xh[0] + g[1] * xh[1]) + (g[2] * xh[2] + g[3] * xh[3]));
+            dx = (g - xh * s2) * inv;
+        }
+        if (ok) SatRow4<T>::st(p.dy, tok * p.ys + j * 64 + c, dx);
+    }
+    if (p.mode != 1) return;
+    // the wave's four row groups hold the same columns: fold them, then the four waves through LDS
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float t = acc[a][e];
+            t += __shfl_xor(t, 16);
+            t += __shfl_xor(t, 32);
+            acc[a][e] = t;
+        }
+    if (lane < 16) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) *reinterpret_cast<f32x4*>(&red[wave][a][c]) = acc[a];
+    }
+    __syncthreads();
+    const int a = threadIdx.x >> 6, col = threadIdx.x & 63;
+    p.part[(long long)blockIdx.x * 256 + a * 64 + col] = (red[0][a][col] + red[1][a][col]) + (red[2][a][col] + red[3][a][col]);
+}
+
+#define SAT_QKN_BWD_ITERS 8
+static int sat_qk_norm_check(const SatQkNormParams& p, int tokens, int dtype, const void* act0, const void* act1, bool need_beta, const char* who) {
+    if (tokens <= 0 || p.ntok <= 0 || tokens % p.ntok != 0 || p.nh <= 0 || p.hq < 0 || p.hq > p.nh) { sat_set_error(who); return 1; }
+    if (dtype != 0 && dtype != 1) { sat_set_error("sat_qk_norm: dtype must be 0 (f32) or 1 (bf16)"); return 1; }
+    if (p.mode != 1 && p.mode != 2) { sat_set_error("sat_qk_norm: mode must be 1 (ln) or 2 (l2)"); return 1; }
+    const int al = dtype == 0 ? 15 : 7;
+    if (((uintptr_t)act0 & al) || ((uintptr_t)act1 & al) || (p.xs % 4) || (p.ys % 4) || p.xs < (long long)p.nh * 64 || p.ys < (long long)p.nh * 64) {
+        sat_set_error("sat_qk_norm: rows must be 16-byte (fp32) / 8-byte (bf16) aligned and hold nh * 64 elements"); return 1;
+    }
+    if (p.mode == 1) {
+        if ((p.hq > 0 && (!p.gq || (need_beta && !p.bq))) || (p.hq < p.nh && (!p.gk || (need_beta && !p.bk)))) { sat_set_error("sat_qk_norm: ln needs gamma / beta tables"); return 1; }
+        if (((uintptr_t)p.gq | (uintptr_t)p.bq | (uintptr_t)p.gk | (uintptr_t)p.bk) & 15) { sat_set_error("sat_qk_norm: tables must be 16-byte aligned"); return 1; }
+    }
+    if (p.cs && (((uintptr_t)p.cs & 31) || p.tab_off < 0)) { sat_set_error("sat_qk_norm: rotary table must be 32-byte aligned"); return 1; }
+    return 0;
+}
+
+// y = rotary(norm(x)) on the first nh heads of every token; stat fp32 ("ln": (2, tokens * nh), "l2": (tokens * nh)) or NULL (no backward).  cs (tab_off + ntok, 16, 2).
+extern "C" int sat_qk_norm_fwd(const void* x, long long xs, void* y, long long ys, const float* q_gamma, const float* q_beta,
+                               const float* k_gamma, const float* k_beta, const float* cs, int tab_off, float* stat, int tokens, int ntok,
+                               int nh, int hq, int mode, float eps, int dtype, void* stream) {
+    SatQkNormParams p{};
+    p.x = x; p.y = y; p.gq = q_gamma; p.bq = q_beta; p.gk = k_gamma; p.bk = k_beta; p.cs = cs; p.stat = stat;
+    p.xs = xs; p.ys = ys; p.ntok = ntok; p.nh = nh; p.hq = hq; p.tab_off = tab_off; p.mode = mode; p.eps = eps;
+    if (sat_qk_norm_check(p, tokens, dtype, x, y, true, "sat_qk_norm_fwd: bad shape")) return 1;
+    p.rows = (long long)tokens * nh;
+    dim3 grid((unsigned)sat_cdivll(p.rows, 16));
+    if (dtype == 0) SAT_LAUNCH(sat_qk_norm_fwd_kernel<float>, grid, dim3(256), stream, p);
+    else SAT_LAUNCH(sat_qk_norm_fwd_kernel<short>, grid, dim3(256), stream, p);
+    return sat_check_launch("sat_qk_norm_fwd");
+}
+
+extern "C" int sat_qk_norm_bwd_nblocks(long long rows) { return (int)sat_cdivll(rows, 16 * SAT_QKN_BWD_ITERS); }
+
+// dy (gradient of sat_qk_norm_fwd's y, same layout) -> gradient of x, IN PLACE.  x, stat: the forward's input and statistics.
+// "ln": part (sat_qk_norm_bwd_nblocks(tokens * nh), 2, 2, 64) fp32 receives per-block [q | k][dgamma | dbeta] sums (sat_reduce_splits).
+extern "C" int sat_qk_norm_bwd(void* dy, long long ys, const void* x, long long xs, const float* q_gamma, const float* k_gamma,
+                               const float* cs, int tab_off, const float* stat, float* part, int tokens, int ntok, int nh, int hq,
+                               int mode, int dtype, void* stream) {
+    SatQkNormParams p{};
+    p.x = x; p.dy = dy; p.gq = q_gamma; p.gk = k_gamma; p.cs = cs; p.stat = const_cast<float*>(stat); p.part = part;
+    p.xs = xs; p.ys = ys; p.ntok = ntok; p.nh = nh; p.hq = hq; p.tab_off = tab_off; p.mode = mode;
+    if (sat_qk_norm_check(p, tokens, dtype, x, dy, false, "sat_qk_norm_bwd: bad shape")) return 1;
+    if (!stat || (mode == 1 && !part)) { sat_set_error("sat_qk_norm_bwd: statistics / partial-sum buffer missing"); return 1; }
+    p.rows = (long long)tokens * nh;
+    p.iters = SAT_QKN_BWD_ITERS;
+    dim3 grid((unsigned)sat_qk_norm_bwd_nblocks(p.rows));
+    if (dtype == 0) SAT_LAUNCH(sat_qk_norm_bwd_kernel<float>, grid, dim3(256), stream, p);
+    else SAT_LAUNCH(sat_qk_norm_bwd_kernel<short>, grid, dim3(256), stream, p);
+    return sat_check_launch("sat_qk_norm_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------
 // SwiGLU and gate/residual
 // ------------------------------------------------------------------------------------------------
 struct SatGluParams {

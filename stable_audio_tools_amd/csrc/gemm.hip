@@ -23,24 +23,30 @@
 #include <type_traits>
 
 
-enum { SAT_EPI_STORE = 0, SAT_EPI_RES = 1, SAT_EPI_GATE_RES = 2, SAT_EPI_SWIGLU = 3, SAT_EPI_QKV = 4 };
+enum { SAT_EPI_STORE = 0, SAT_EPI_RES = 1, SAT_EPI_GATE_RES = 2, SAT_EPI_SWIGLU = 3, SAT_EPI_QKV = 4, SAT_EPI_QKV_NORM = 5 };
+// SAT_EPI_QKV_NORM = SAT_EPI_QKV with the per-head q / k normalisation of Attention(qk_norm=...) (transformer.py:374-376, :485-489) between
+// the projection and the rotary; norm_mode: 1 = "ln" (LayerNorm over the 64 head dims, affine, biased variance), 2 = "l2" (x / max(|x|, 1e-12))
+#define SAT_EPI_IS_QKV(E) ((E) == SAT_EPI_QKV || (E) == SAT_EPI_QKV_NORM)
 
 struct SatGemmParams {
     const short* A;       // (M, K) bf16
     const short* B;       // (N, K) bf16
-    void* C;              // (M, ldc) bf16 or fp32; split-K: slab z at C + z * M * ldc (fp32)
+    // (SAT_EPI_QKV_NORM keeps its tables and constants in slots the head-split epilogues never read — kn_beta / qn_gamma / qn_beta /
+    // kn_gamma / norm_mode / norm_eps below — so the kernel-argument block of every other instantiation stays what it was)
+    union { void* C; const float* kn_beta; };   // (M, ldc) bf16 or fp32; split-K: slab z at C + z * M * ldc (fp32)
     const float* bias;    // (N) fp32 or null
-    const void* res;      // (M, ldr) dtype of C: added after the gate
-    const void* gate;     // (M / rows_per_gate, ldg) dtype of C: v * sigmoid(1 - gate)   (transformer.py:684, :699)
-    void* pre;            // SWIGLU: optional (M, ldp) copy of the pre-activation [x | gate] for the backward
+    union { const void* res; const float* qn_gamma; };   // (M, ldr) dtype of C: added after the gate
+    union { const void* gate; const float* qn_beta; };   // (M / rows_per_gate, ldg) dtype of C: v * sigmoid(1 - gate)   (transformer.py:684, :699)
+    union { void* pre; const float* kn_gamma; };         // SWIGLU: optional (M, ldp) copy of the pre-activation [x | gate] for the backward
     const short* zeros;   // >= 16 bytes of zeros: source of the k-chunks past K
     const float* alpha;   // device scalar multiplied into the accumulators before the epilogue (fp8 de-quantisation), or null
     const float* row_alpha; // (M) per-row factor applied with it (fp8 activations quantised per row: sat_quant_fp8_rows), or null
     const float* col_alpha; // (N) per-COLUMN factor = per-output-channel de-quantisation scale of B's rows (fp8 weights quantised row by
                             // row, round 6: one scale per output channel instead of one per tensor), or null
-    long long lda, ldb, ldc, ldr, ldg, ldp;
+    long long lda, ldb, ldc, ldr, ldg;
+    union { long long ldp; float norm_eps; };
     int M, N, K;
-    int rows_per_gate;
+    union { int rows_per_gate; int norm_mode; };
     int klen;             // K range of one blockIdx.y slice (multiple of 64; == padded K without split-K)
     int ntm, ntn;
     // QKV epilogue: rotary + attention planes (attention.hip layouts)
@@ -122,18 +128,18 @@ SAT_DEVICE float sat_gemm_sigmoid(float x) {
 // gate loads and the stores are 8- or 16-byte accesses that cover whole 128-byte row segments.
 template <int EPI>
 SAT_DEVICE bool sat_gemm_window_is_v(const SatGemmParams& p, int nwin) {
-    if constexpr (EPI == SAT_EPI_QKV) return nwin < p.N && nwin / (p.heads * 64) + p.sec0 == 2;
+    if constexpr (SAT_EPI_IS_QKV(EPI)) return nwin < p.N && nwin / (p.heads * 64) + p.sec0 == 2;
     else return false;
 }
 
 template <int EPI, bool F32OUT>
 SAT_DEVICE void sat_gemm_epilogue_window(const SatGemmParams& p, const float* ep, int mrow0, int nwin, int glu_col0, int glu_f, int lane) {
     int wb0 = 0, wt0 = 0;                              // QKV: (batch item, token) of the window's first row — ONE division per window
-    if constexpr (EPI == SAT_EPI_QKV) {                   // (round 4: the per-lane m / ntok, m % ntok of every pass were the bulk of this epilogue)
+    if constexpr (SAT_EPI_IS_QKV(EPI)) {                  // (round 4: the per-lane m / ntok, m % ntok of every pass were the bulk of this epilogue)
         wb0 = mrow0 / p.ntok;
         wt0 = mrow0 - wb0 * p.ntok;
     }
-    if constexpr (EPI == SAT_EPI_QKV) {
+    if constexpr (SAT_EPI_IS_QKV(EPI)) {
         // a 64-column window is one head of q, k or v (wave-uniform).  v goes out TRANSPOSED (nb, H, 64, Np): the window was
         // staged as [64 d][33] so that a lane reads 4 consecutive tokens of one head dim (odd stride: conflict free)
         if (sat_gemm_window_is_v<EPI>(p, nwin)) {
@@ -238,7 +244,7 @@ SAT_DEVICE void sat_gemm_epilogue_window(const SatGemmParams& p, const float* ep
     } else {
         // (QKV: two passes in flight — with all eight unrolled the rotary's table loads, partner columns and row factors of every pass are
         // live at once: the 256 x 256 kernel spilled 113 registers, 239 -> 844 us at M = 12290)
-        constexpr int PU = (EPI == SAT_EPI_QKV) ? 2 : 8;
+        constexpr int PU = SAT_EPI_IS_QKV(EPI) ? 2 : 8;
 #pragma unroll 1
         for (int p0 = 0; p0 < 8; p0 += PU)
 #pragma unroll
@@ -248,6 +254,62 @@ SAT_DEVICE void sat_gemm_epilogue_window(const SatGemmParams& p, const float* ep
             const int m = mrow0 + rr;
             const int n = nwin + cc;
             f32x4 v = *(const f32x4*)(ep + rr * 64 + cc);
+            if constexpr (EPI == SAT_EPI_QKV_NORM) {
+                // q / k head normalisation: the window is one head, its row rr lives in this 16-lane group (4 columns per lane), so the
+                // row statistics are a 16-lane butterfly — taken by every lane (rows / columns past the matrix included: finite LDS
+                // values, never stored) so that the shuffles are not under a divergent branch.  Two passes: mean, then centred squares.
+                const bool inside = m < p.M && n < p.N;
+                if (inside) {
+                    if (p.row_alpha) v *= p.row_alpha[m];
+                    if (p.col_alpha) v *= *(const f32x4*)(p.col_alpha + n);
+                    if (p.bias) v += *(const f32x4*)(p.bias + n);
+                }
+                float nmean = 0.f, nrs;
+                if (p.norm_mode == 1) {
+                    float s = (v[0] + v[1]) + (v[2] + v[3]);
+#pragma unroll
+                    for (int msk = 8; msk >= 1; msk >>= 1) s += __shfl_xor(s, msk);
+                    nmean = s * (1.0f / 64.0f);
+                    v -= nmean;
+                }
+                float ss = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+#pragma unroll
+                for (int msk = 8; msk >= 1; msk >>= 1) ss += __shfl_xor(ss, msk);
+                nrs = (p.norm_mode == 1) ? 1.0f / sqrtf(ss * (1.0f / 64.0f) + p.norm_eps) : 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+                if (inside) {
+                    const int hd = p.heads * 64;
+                    const int nsec = nwin / hd;                                            // (wave-uniform: a window is one head)
+                    const int which = nsec + p.sec0, h = (nwin - nsec * hd) >> 6, d = n & 63;   // 0 q, 1 k
+                    const float* ng = (which == 0) ? p.qn_gamma : p.kn_gamma;
+                    const float* nb = (which == 0) ? p.qn_beta : p.kn_beta;
+                    v *= nrs;
+                    if (p.norm_mode == 1) v = v * *(const f32x4*)(ng + d) + *(const f32x4*)(nb + d);
+                    int b = wb0, t = wt0 + rr;
+                    while (t >= p.ntok) { t -= p.ntok; ++b; }
+                    if (p.rope_cs && d < 32) {
+                        // the rotary's partner column d ^ 16 comes raw from the window: same row factor / mean / rstd, its own column's
+                        // de-quantisation scale, bias, gamma and beta
+                        f32x4 o;
+                        f32x4 pv = *(const f32x4*)(ep + rr * 64 + (cc ^ 16));
+                        if (p.row_alpha) pv *= p.row_alpha[m];
+                        if (p.col_alpha) pv *= *(const f32x4*)(p.col_alpha + (n ^ 16));
+                        if (p.bias) pv += *(const f32x4*)(p.bias + (n ^ 16));
+                        pv = (pv - nmean) * nrs;
+                        if (p.norm_mode == 1) pv = pv * *(const f32x4*)(ng + (d ^ 16)) + *(const f32x4*)(nb + (d ^ 16));
+                        const float* cs = p.rope_cs + ((long long)(t + p.rope_off) * 16 + (d & 15)) * 2;
+                        const f32x4 cs0 = *(const f32x4*)cs, cs1 = *(const f32x4*)(cs + 4);
+                        const float cc_[4] = {cs0[0], cs0[2], cs1[0], cs1[2]}, ss_[4] = {cs0[1], cs0[3], cs1[1], cs1[3]};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float c = cc_[e], s = ss_[e];
+                            o[e] = (d < 16) ? v[e] * c - pv[e] * s : v[e] * c + pv[e] * s;
+                        }
+                        v = o;
+                    }
+                    short* dst = (which == 0) ? p.q_rm : p.k_rm;
+                    sat_store4<false>(dst, (((long long)b * p.heads + h) * p.npad + t) * 64 + d, v);
+                }
+            } else
             if (m < p.M && n < p.N) {
                 if (p.row_alpha) v *= p.row_alpha[m];
                 if (p.col_alpha) v *= *(const f32x4*)(p.col_alpha + n);
@@ -1026,6 +1088,10 @@ static int sat_gemm8_launch(SatGemmParams& p, int epi, int f32out, int splits, v
     SAT_GEMM8_CASE(SAT_EPI_SWIGLU, true)
     SAT_GEMM8_CASE(SAT_EPI_QKV, false)
 #undef SAT_GEMM8_CASE
+    if (epi == SAT_EPI_QKV_NORM && !f32out && !fp8) {        // (bf16 operands only: the fp8 heads projection has no norm epilogue)
+        SAT_LAUNCH((sat_gemm8_kernel<BN, R0, R1, NST, SAT_EPI_QKV_NORM, false, false>), grid, block, stream, p);
+        return sat_check_launch("sat_gemm (eight-wave ring, qk norm)");
+    }
     sat_set_error("sat_gemm: unsupported epilogue / output type");
     return 1;
 }
@@ -1076,6 +1142,12 @@ static int sat_gemm_launch(SatGemmParams& p, int epi, int f32out, int splits, vo
     SAT_GEMM_CASE(SAT_EPI_SWIGLU, true)
     SAT_GEMM_CASE(SAT_EPI_QKV, false)
 #undef SAT_GEMM_CASE
+    if constexpr (!FP8) {
+        if (epi == SAT_EPI_QKV_NORM && !f32out) {
+            SAT_LAUNCH((sat_gemm_kernel<BM, BN, WGM, WGN, NSTAGE, PIPE, SAT_EPI_QKV_NORM, false, false>), grid, block, stream, p);
+            return sat_check_launch("sat_gemm_bf16 (qk norm)");
+        }
+    }
     sat_set_error("sat_gemm_bf16: unsupported epilogue / output type");
     return 1;
 }
@@ -1086,6 +1158,9 @@ static int sat_gemm_launch(SatGemmParams& p, int epi, int f32out, int splits, vo
 //   sat_gemm8_kernel (eight waves in two groups one barrier apart, one interval pair per K-step, 3- or 4-stage ring):
 //   7 = 160 x 256, 8 = 128 x 128.
 static int sat_gemm_dispatch(SatGemmParams& p, int epi, int f32out, int splits, int tile, void* stream) {
+    // (the norm epilogue has no 256 x 256 instantiation: that kernel keeps 2 registers in scratch with the head-split epilogue already,
+    // and the new kind ships without any — callers choose among tiles 0, 7 and 8)
+    if (epi == SAT_EPI_QKV_NORM && tile == 4) { sat_set_error("sat_gemm_qkv_norm_bf16: tile must be 0, 7 or 8 (no 256 x 256 norm epilogue)"); return 1; }
     if (tile == 4) return sat_gemm256_launch(p, epi, f32out, splits, stream);
     if (tile == 7) return sat_gemm8_launch<256, 96, 64, 3>(p, epi, f32out, splits, stream);
     if (tile == 8) return sat_gemm8_launch<128, 32, 32, 4>(p, epi, f32out, splits, stream);
@@ -1150,6 +1225,35 @@ extern "C" int sat_gemm_qkv_bf16(const void* A, long long lda, const void* B, lo
     p.rope_cs = rope_cs; p.rope_off = rope_off; p.q_rm = (short*)q_rm; p.k_rm = (short*)k_rm; p.v_tr = (short*)v_tr;
     p.ntok = ntok; p.npad = npad; p.heads = heads; p.sec0 = sec0;
     return sat_gemm_dispatch(p, SAT_EPI_QKV, 0, 1, tile, stream);
+}
+
+// sat_gemm_qkv_bf16 with Attention(qk_norm=...) in the epilogue: every q / k head row (64 values) is normalised after the projection and
+// before the rotary; v is untouched.  mode 1 = "ln": LayerNorm with fp32 statistics, biased variance, eps, and the (64) fp32 tables
+// q_gamma / q_beta (q heads) and k_gamma / k_beta (k heads), 16-byte aligned; mode 2 = "l2": x / max(||x||_2, 1e-12), tables NULL.
+// tile: 0, 7 or 8 (the 256 x 256 kernel has no norm instantiation).
+extern "C" int sat_gemm_qkv_norm_bf16(const void* A, long long lda, const void* B, long long ldb, const float* rope_cs, int rope_off,
+                                      void* q_rm, void* k_rm, void* v_tr, const void* zeros, int nb, int ntok, int npad, int heads,
+                                      int K, int sec0, int nsec, int tile, int mode, const float* q_gamma, const float* q_beta,
+                                      const float* k_gamma, const float* k_beta, float eps, void* stream) {
+    if (nb <= 0 || ntok <= 0 || heads <= 0 || K <= 0 || npad < ntok) { sat_set_error("sat_gemm_qkv_norm_bf16: bad shape"); return 1; }
+    if ((K & 7) || (lda & 7) || (ldb & 7)) { sat_set_error("sat_gemm_qkv_norm_bf16: K, lda, ldb must be multiples of 8"); return 1; }
+    if (sec0 < 0 || nsec < 1 || sec0 + nsec > 3) { sat_set_error("sat_gemm_qkv_norm_bf16: bad section range"); return 1; }
+    if ((sec0 == 0 && !q_rm) || (sec0 <= 1 && sec0 + nsec > 1 && !k_rm) || (sec0 + nsec > 2 && !v_tr)) { sat_set_error("sat_gemm_qkv_norm_bf16: missing plane"); return 1; }
+    if (mode != 1 && mode != 2) { sat_set_error("sat_gemm_qkv_norm_bf16: mode must be 1 (ln) or 2 (l2)"); return 1; }
+    if (mode == 1) {
+        const bool has_q = sec0 == 0, has_k = sec0 <= 1 && sec0 + nsec > 1;
+        if ((has_q && (!q_gamma || !q_beta)) || (has_k && (!k_gamma || !k_beta))) { sat_set_error("sat_gemm_qkv_norm_bf16: ln needs gamma / beta tables"); return 1; }
+        if (((uintptr_t)q_gamma | (uintptr_t)q_beta | (uintptr_t)k_gamma | (uintptr_t)k_beta) & 15) { sat_set_error("sat_gemm_qkv_norm_bf16: tables must be 16-byte aligned"); return 1; }
+    }
+    SatGemmParams p{};
+    p.A = (const short*)A; p.B = (const short*)B; p.zeros = (const short*)zeros;
+    p.lda = lda; p.ldb = ldb;
+    p.M = nb * ntok; p.N = nsec * heads * 64; p.K = K;
+    p.klen = sat_cdiv(K, 64) * 64;
+    p.rope_cs = rope_cs; p.rope_off = rope_off; p.q_rm = (short*)q_rm; p.k_rm = (short*)k_rm; p.v_tr = (short*)v_tr;
+    p.ntok = ntok; p.npad = npad; p.heads = heads; p.sec0 = sec0;
+    p.qn_gamma = q_gamma; p.qn_beta = q_beta; p.kn_gamma = k_gamma; p.kn_beta = k_beta; p.norm_mode = mode; p.norm_eps = eps;
+    return sat_gemm_dispatch(p, SAT_EPI_QKV_NORM, 0, 1, tile, stream);
 }
 
 // Second half of a split-K projection: out[m][n] = sum_z slabs[z][m][n] (+ bias[n]) (+ res[m][n]), written in the output dtype.

@@ -1215,6 +1215,72 @@ class SatOps:
                                           cs.shape[0] - n, int(transpose), dt, self._stream(t)))
         return t
 
+    QK_NORM_MODES = {"ln": 1, "l2": 2}
+
+    def _qk_tables(self, mode, tables, nh, hq):
+        """(mode code, [q gamma, q beta, k gamma, k beta]) for the qk-norm kernels: fp32 (64,) tensors for "ln", Nones for "l2"."""
+        code = self.QK_NORM_MODES[mode]
+        tables = list(tables) if tables is not None else [None] * 4
+        if code == 1:
+            need = ([0, 1] if hq > 0 else []) + ([2, 3] if hq < nh else [])
+            for i in need:
+                if tables[i] is None or tables[i].numel() != 64:
+                    raise ValueError("qk_norm 'ln' needs (64,) fp32 gamma / beta tables")
+            self._f32(*tables)
+        else:
+            tables = [None] * 4
+        return code, tables
+
+    def qk_norm(self, x, nh, hq, mode, tables=None, cs=None, eps=1e-6, out=None, save_stats=False):
+        """Per-head q / k normalisation + rotary (sat_qk_norm_fwd).  x: (B, N, C) with C >= nh*64, last dim contiguous: the first nh heads
+        of every token are normalised ("ln": LayerNorm over the 64 head dims with tables = (q gamma, q beta, k gamma, k beta), heads < hq
+        take the q pair; "l2": x / max(|x|, 1e-12)), then rotated with cs ((>= N, 16, 2) table or None), and written to `out` (same
+        batch / token shape, C' >= nh*64; default: a new tensor like x whose columns past nh*64 are NOT written).
+        Returns out, or (out, stat) with save_stats: fp32, (2, B*N*nh) = mean | rstd for "ln", (1, B*N*nh) = 1 / max(|x|, 1e-12) for "l2"."""
+        dt = self._dt(x, out)
+        b, n, c = x.shape
+        if out is None:
+            out = torch.empty_like(x, memory_format=torch.contiguous_format)
+        if x.stride(2) != 1 or out.stride(2) != 1 or x.stride(0) != n * x.stride(1) or out.stride(0) != n * out.stride(1) \
+                or out.shape[:2] != x.shape[:2] or min(c, out.shape[2]) < nh * 64:
+            raise ValueError("qk_norm: bad layout")
+        code, (gq, bq, gk, bk) = self._qk_tables(mode, tables, nh, hq)
+        if cs is not None:
+            self._f32(cs)
+        stat = torch.empty(2 if code == 1 else 1, b * n * nh, dtype=torch.float32, device=x.device) if save_stats else None
+        self._chk(self.lib.sat_qk_norm_fwd(_ptr(x), x.stride(1), _ptr(out), out.stride(1), _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk), _ptr(cs),
+                                           (cs.shape[0] - n) if cs is not None else 0, _ptr(stat), b * n, n, nh, hq, code, float(eps), dt,
+                                           self._stream(x)))
+        return (out, stat) if save_stats else out
+
+    def qk_norm_bwd_(self, dy, x, stat, nh, hq, mode, tables=None, cs=None):
+        """Backward of qk_norm, IN PLACE on dy ((B, N, C') gradient of `out`): the first nh heads of every token become the gradient of x
+        (inverse rotary, then the norm's backward from the raw x and the saved statistics).  Returns (dgq, dbq, dgk, dbk) fp32 (64,)
+        for "ln" (None for a pair no head uses), None for "l2"."""
+        dt = self._dt(dy, x)
+        b, n, _ = x.shape
+        if x.stride(2) != 1 or dy.stride(2) != 1 or x.stride(0) != n * x.stride(1) or dy.stride(0) != n * dy.stride(1) \
+                or dy.shape[:2] != x.shape[:2] or min(x.shape[2], dy.shape[2]) < nh * 64:
+            raise ValueError("qk_norm_bwd_: bad layout")
+        code, (gq, _, gk, _) = self._qk_tables(mode, tables, nh, hq)
+        self._f32(stat)
+        if stat.numel() != (2 if code == 1 else 1) * b * n * nh:
+            raise ValueError("qk_norm_bwd_: statistics of another call")
+        if cs is not None:
+            self._f32(cs)
+        part = None
+        if code == 1:
+            nblk = self.lib.sat_qk_norm_bwd_nblocks(b * n * nh)
+            part = torch.empty(nblk, 256, dtype=torch.float32, device=x.device)
+        self._chk(self.lib.sat_qk_norm_bwd(_ptr(dy), dy.stride(1), _ptr(x), x.stride(1), _ptr(gq), _ptr(gk), _ptr(cs),
+                                           (cs.shape[0] - n) if cs is not None else 0, _ptr(stat), _ptr(part), b * n, n, nh, hq, code, dt,
+                                           self._stream(x)))
+        if code != 1:
+            return None
+        sums = self._reduce_rows(part, nblk, 256)
+        return (sums[0:64] if hq > 0 else None, sums[64:128] if hq > 0 else None,
+                sums[128:192] if hq < nh else None, sums[192:256] if hq < nh else None)
+
     def swiglu(self, xin):
         dt = self._dt(xin)
         f = xin.shape[-1] // 2
@@ -1317,15 +1383,15 @@ class SatOps:
             t += 4.0 + splits * m * n * 4 / 4e6      # sat_splitk_epilogue: launch + the slabs read back at ~4 TB/s
         return t
 
-    def _pick_tile(self, m, n, splits=1, k=None):
+    def _pick_tile(self, m, n, splits=1, k=None, exclude=()):
         """Workgroup tile of a projection.  Round 4: the cheapest of the shipped tiles under _TILE_MODEL — 256 x 256 (sat_gemm256_kernel)
         for the many-tile shapes, 160 x 256 where 256-row tiles leave CUs idle (QKV at M = 2050: 144 full tiles -> 234 workgroups),
         128 x 128 on eight waves for the 1536 -> 1536 projections (sat_gemm8_kernel), the four-wave 128 x 128 kernel for the rest."""
-        if self.gemm_tile is not None:
+        if self.gemm_tile is not None and self.gemm_tile not in exclude:
             return self.gemm_tile
         if k is None:
-            return 4 if splits == 1 and ((m + 255) // 256) * ((n + 255) // 256) >= 150 else 0
-        return min(self._TILE_MODEL, key=lambda t: (self._tile_cost(t, m, n, k, splits), t))
+            return 4 if 4 not in exclude and splits == 1 and ((m + 255) // 256) * ((n + 255) // 256) >= 150 else 0
+        return min((t for t in self._TILE_MODEL if t not in exclude), key=lambda t: (self._tile_cost(t, m, n, k, splits), t))
 
     def gemm_bf16(self, a, b, bias=None, res=None, gate=None, rows_per_gate=0, epilogue=0, out_dtype=torch.bfloat16, want_pre=False,
                   splits=1, out=None):
@@ -1410,11 +1476,13 @@ class SatOps:
 
     gemm_splitk = None
 
-    def gemm_heads_bf16(self, x, w, cs, heads, nb, ntok, sec0, nsec, reuse=None):
+    def gemm_heads_bf16(self, x, w, cs, heads, nb, ntok, sec0, nsec, reuse=None, qk_norm=None, norm_tables=None, norm_eps=1e-6):
         """Attention input projection with head split / rotary / plane layout fused (sat_gemm_qkv_bf16): x (nb*ntok, K) bf16,
         w (nsec*heads*64, K) bf16, cs (>= ntok, 16, 2) fp32 rotary table or None.  Sections sec0 .. sec0+nsec-1 of (q, k, v).
         Returns dict(q=, k= (nb,H,Np,64), v_tr= (nb,H,64,Np)) with the produced planes (bf16 bits as int16, zero padded).
-        reuse: a hashable tag -> the planes live in a per-ops cache (only safe when nothing keeps them for a backward)."""
+        reuse: a hashable tag -> the planes live in a per-ops cache (only safe when nothing keeps them for a backward).
+        qk_norm: None, or "ln" / "l2" — the q and k heads are normalised in the same epilogue, before the rotary
+        (sat_gemm_qkv_norm_bf16; still one launch); norm_tables = (q gamma, q beta, k gamma, k beta) fp32 (64,) for "ln"."""
         if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
             raise TypeError("gemm_heads_bf16 takes bf16 operands")
         if x.stride(1) != 1 or w.stride(1) != 1 or w.shape[0] != nsec * heads * 64 or x.shape[0] != nb * ntok:
@@ -1427,6 +1495,15 @@ class SatOps:
                              else torch.zeros(shape, dtype=torch.int16, device=x.device))
         if cs is not None:
             self._f32(cs)
+        if qk_norm is not None and qk_norm != "none":
+            has_q, has_k = sec0 == 0, sec0 <= 1 < sec0 + nsec
+            tile = self._pick_tile(nb * ntok, nsec * heads * 64, 1, x.shape[1], exclude=(4,))     # (no 256 x 256 norm epilogue)
+            code, (gq, bq, gk, bk) = self._qk_tables(qk_norm, norm_tables, int(has_q) + int(has_k), int(has_q))
+            self._chk(self.lib.sat_gemm_qkv_norm_bf16(_ptr(x), x.stride(0), _ptr(w), w.stride(0), _ptr(cs), (cs.shape[0] - ntok) if cs is not None else 0,
+                                                      _ptr(out.get("q")), _ptr(out.get("k")), _ptr(out.get("v_tr")), _ptr(self._zeros_page(x.device)),
+                                                      nb, ntok, npad, heads, x.shape[1], sec0, nsec, tile, code,
+                                                      _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk), float(norm_eps), self._stream(x)))
+            return out
         self._chk(self.lib.sat_gemm_qkv_bf16(_ptr(x), x.stride(0), _ptr(w), w.stride(0), _ptr(cs), (cs.shape[0] - ntok) if cs is not None else 0,
                                              _ptr(out.get("q")), _ptr(out.get("k")), _ptr(out.get("v_tr")), _ptr(self._zeros_page(x.device)),
                                              nb, ntok, npad, heads, x.shape[1], sec0, nsec, self._pick_tile(nb * ntok, nsec * heads * 64, 1, x.shape[1]),

@@ -8,10 +8,13 @@ global_cond_embedder).
 Execution: LayerNorm(+adaLN modulate), partial rotary, attention (self and GQA cross), SwiGLU and the
 gate/residual epilogue are HIP kernels (csrc/dit_ops.hip, csrc/attention.hip); every projection is
 linear.Linear on the native MFMA GEMM (csrc/gemm.hip) with the head split / rotary / SwiGLU / gate /
-residual work of the block fused into the GEMM epilogues — no library GEMM.  Options of the reference that
-the Stable Audio DiT configs never enable (qk_norm, differential attention, conformer, layer_scale,
-memory tokens, sliding window, causal, flex-attention masks, abs/sinusoidal position embeddings)
-raise NotImplementedError.
+residual work of the block fused into the GEMM epilogues — no library GEMM.  Attention(qk_norm="ln" | "l2")
+(attn_kwargs: {"qk_norm": ...}; the per-head q / k normalisation before the rotary, transformer.py:374-376,
+:485-489) runs inside the same projection epilogue in bf16 inference (sat_gemm_qkv_norm_bf16) and on the
+sat_qk_norm_fwd / sat_qk_norm_bwd kernels in training and fp32.  Options of the reference that the Stable
+Audio DiT configs never enable (qk_norm="dyt", differential attention, conformer, layer_scale, memory
+tokens, sliding window, causal, flex-attention masks, abs/sinusoidal position embeddings) raise
+NotImplementedError.
 
 Forward AND backward run on the HIP kernels: every fused operator is a torch.autograd.Function whose
 backward calls the matching kernel (LayerNorm+adaLN, rotary transpose, attention dQ / dK,dV with
@@ -219,14 +222,33 @@ class _SelfAttnFn(torch.autograd.Function):
     zero-filled (B, N, 3*H*dh) tensors, three strided copies into their thirds, two adds and a clone for the in-place rotary — nine
     activation-sized launches per layer; here dq / dk / dv leave the backward kernels as one (3, B, H, N, dh) buffer that ONE strided
     copy turns into the projection's layout, and the inverse rotary runs in place on that copy.
-    `qkv` is rotated in place: it is the output of the projection GEMM, which nothing else reads (autograd raises if something saved it)."""
+    `qkv` is rotated in place: it is the output of the projection GEMM, which nothing else reads (autograd raises if something saved it).
+    With qk_norm (norm = (mode, fp32 tables), qn = the q_norm / k_norm parameters the gradients go to) the normalised + rotated q / k
+    heads go to a buffer of their own (sat_qk_norm_fwd) and the raw projection is kept: the backward recomputes x-hat from it — never
+    from the output and gamma, which may be zero — in the one pass that also undoes the rotary (sat_qk_norm_bwd, in place on dqkv)."""
 
     @staticmethod
-    def forward(ctx, qkv, cs, heads, dh, scale):
+    def forward(ctx, qkv, cs, heads, dh, scale, norm=None, *qn):
         ops = _ops()
         b, n, _ = qkv.shape
         if not qkv.is_contiguous():
             qkv = qkv.contiguous()
+        ctx.norm = norm
+        if norm is not None:
+            mode, tabs = norm
+            need = any(ctx.needs_input_grad)
+            qk = torch.empty(b, n, 2 * heads * dh, dtype=qkv.dtype, device=qkv.device)
+            res = ops.qk_norm(qkv, 2 * heads, heads, mode, tabs, cs, out=qk, save_stats=need)
+            qk5 = qk.view(b, n, 2, heads, dh)
+            q, k = qk5[:, :, 0].permute(0, 2, 1, 3), qk5[:, :, 1].permute(0, 2, 1, 3)
+            v = qkv.view(b, n, 3, heads, dh)[:, :, 2].permute(0, 2, 1, 3)
+            if need:
+                o, lse, planes = ops.attention(q, k, v, scale, return_planes=True)
+                ctx.ops, ctx.scale, ctx.planes, ctx.meta = ops, scale, planes, (b, n, heads, dh)
+                ctx.qn_dtypes = [t.dtype for t in qn]
+                ctx.save_for_backward(o, lse, cs, qkv, res[1], *(tabs or ()))
+                return o
+            return ops.attention(q, k, v, scale)
         if cs is not None:
             ops.rope_apply_(qkv[..., 0:2 * heads * dh].unflatten(-1, (2 * heads, dh)), cs)     # q and k heads in one launch
         q5 = qkv.view(b, n, 3, heads, dh)
@@ -240,40 +262,63 @@ class _SelfAttnFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        o, lse, cs = ctx.saved_tensors
+        o, lse, cs = ctx.saved_tensors[:3]
         b, n, heads, dh = ctx.meta
         buf = torch.empty(3, b, heads, n, dh, dtype=o.dtype, device=o.device)
         ctx.ops.attention_bwd(ctx.planes, o, g.contiguous(), lse, ctx.scale, heads, n, out=(buf[0], buf[1], buf[2]))
         dqkv = torch.empty(b, n, 3, heads, dh, dtype=o.dtype, device=o.device)
         dqkv.copy_(buf.permute(1, 3, 0, 2, 4))
         dqkv = dqkv.view(b, n, 3 * heads * dh)
+        if ctx.norm is not None:
+            qkv, stat = ctx.saved_tensors[3:5]
+            grads = ctx.ops.qk_norm_bwd_(dqkv, qkv, stat, 2 * heads, heads, ctx.norm[0], ctx.saved_tensors[5:] or None, cs)
+            return (dqkv, None, None, None, None, None) + _qn_grads(grads, ctx.qn_dtypes)
         if cs is not None:
             ctx.ops.rope_apply_(dqkv[..., 0:2 * heads * dh].unflatten(-1, (2 * heads, dh)), cs, transpose=True)
-        return dqkv, None, None, None, None
+        return dqkv, None, None, None, None, None
 
 
 class _CrossAttnFn(torch.autograd.Function):
     """The training path of the cross-attention core as one autograd node: q (B, N, H*dh) and the fused key / value projection
-    kv (B, M, 2*Hkv*dh) in, merged heads out; the backward assembles dkv with one strided copy (see _SelfAttnFn)."""
+    kv (B, M, 2*Hkv*dh) in, merged heads out; the backward assembles dkv with one strided copy (see _SelfAttnFn).
+    With qk_norm (norm, qn as in _SelfAttnFn) q and the k half of kv are normalised into buffers of their own; the raw projections stay."""
 
     @staticmethod
-    def forward(ctx, q2, kv, heads, kv_heads, dh, scale):
+    def forward(ctx, q2, kv, heads, kv_heads, dh, scale, norm=None, *qn):
         ops = _ops()
         b, n, _ = q2.shape
         m = kv.shape[1]
-        q = q2.view(b, n, heads, dh).permute(0, 2, 1, 3)
-        kv5 = kv.contiguous().view(b, m, 2, kv_heads, dh)
-        k, v = kv5[:, :, 0].permute(0, 2, 1, 3), kv5[:, :, 1].permute(0, 2, 1, 3)
-        if any(ctx.needs_input_grad[:2]):
+        need = any(ctx.needs_input_grad)
+        ctx.norm = norm
+        saved = ()
+        kvc = kv.contiguous()
+        kv5 = kvc.view(b, m, 2, kv_heads, dh)
+        v = kv5[:, :, 1].permute(0, 2, 1, 3)
+        if norm is not None:
+            mode, tabs = norm
+            q2c = q2.contiguous()
+            qn_ = torch.empty_like(q2c)
+            kn_ = torch.empty(b, m, kv_heads * dh, dtype=kv.dtype, device=kv.device)
+            rq = ops.qk_norm(q2c, heads, heads, mode, tabs, None, out=qn_, save_stats=need)
+            rk = ops.qk_norm(kvc, kv_heads, 0, mode, tabs, None, out=kn_, save_stats=need)
+            q = qn_.view(b, n, heads, dh).permute(0, 2, 1, 3)
+            k = kn_.view(b, m, kv_heads, dh).permute(0, 2, 1, 3)
+            if need:
+                saved = (q2c, kvc, rq[1], rk[1]) + tuple(tabs or ())
+            ctx.qn_dtypes = [t.dtype for t in qn]
+        else:
+            q = q2.view(b, n, heads, dh).permute(0, 2, 1, 3)
+            k = kv5[:, :, 0].permute(0, 2, 1, 3)
+        if need:
             o, lse, planes = ops.attention(q, k, v, scale, return_planes=True)
             ctx.ops, ctx.scale, ctx.planes, ctx.meta = ops, scale, planes, (b, n, m, heads, kv_heads, dh)
-            ctx.save_for_backward(o, lse)
+            ctx.save_for_backward(o, lse, *saved)
             return o
         return ops.attention(q, k, v, scale)
 
     @staticmethod
     def backward(ctx, g):
-        o, lse = ctx.saved_tensors
+        o, lse = ctx.saved_tensors[:2]
         b, n, m, heads, kv_heads, dh = ctx.meta
         buf = torch.empty(2, b, kv_heads, m, dh, dtype=o.dtype, device=o.device)
         dq = torch.empty(b, heads, n, dh, dtype=o.dtype, device=o.device)
@@ -282,7 +327,80 @@ class _CrossAttnFn(torch.autograd.Function):
         dq2.copy_(dq.permute(0, 2, 1, 3))
         dkv = torch.empty(b, m, 2, kv_heads, dh, dtype=o.dtype, device=o.device)
         dkv.copy_(buf.permute(1, 3, 0, 2, 4))
-        return dq2.view(b, n, heads * dh), dkv.view(b, m, 2 * kv_heads * dh), None, None, None, None
+        dq2, dkv = dq2.view(b, n, heads * dh), dkv.view(b, m, 2 * kv_heads * dh)
+        if ctx.norm is not None:
+            q2, kv, sq, sk = ctx.saved_tensors[2:6]
+            tabs = ctx.saved_tensors[6:] or None
+            gq = ctx.ops.qk_norm_bwd_(dq2, q2, sq, heads, heads, ctx.norm[0], tabs, None)
+            gk = ctx.ops.qk_norm_bwd_(dkv, kv, sk, kv_heads, 0, ctx.norm[0], tabs, None)
+            grads = (gq[0], gq[1], gk[2], gk[3]) if gq is not None else None
+            return (dq2, dkv, None, None, None, None, None) + _qn_grads(grads, ctx.qn_dtypes)
+        return dq2, dkv, None, None, None, None, None
+
+
+def _qn_grads(grads, dtypes):
+    """The q_norm / k_norm parameter gradients of a qk_norm_bwd_ call in the parameters' dtypes ("l2": there are no parameters)."""
+    if grads is None:
+        return ()
+    return tuple(g.to(dt) for g, dt in zip(grads, dtypes))
+
+
+class _QKNormFn(torch.autograd.Function):
+    """qk_norm (+ rotary) on the first nh heads of a (B, N, C) projection as a node of its own — the unfused path (train_fused_nodes
+    off), where it takes the place of _RopeQKFn.  The columns past the normalised heads (v) are copied through."""
+
+    @staticmethod
+    def forward(ctx, x, cs, nh, hq, norm, *qn):
+        ops = _ops()
+        mode, tabs = norm
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        if x.shape[-1] > nh * 64:
+            out[..., nh * 64:] = x[..., nh * 64:]
+        need = any(ctx.needs_input_grad)
+        res = ops.qk_norm(x, nh, hq, mode, tabs, cs, out=out, save_stats=need)
+        if need:
+            ctx.save_for_backward(x, res[1], cs, *(tabs or ()))
+            ctx.meta = (nh, hq, mode, ops, [t.dtype for t in qn])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, stat, cs = ctx.saved_tensors[:3]
+        nh, hq, mode, ops, dtypes = ctx.meta
+        g = g.clone(memory_format=torch.contiguous_format)
+        grads = ops.qk_norm_bwd_(g, x, stat, nh, hq, mode, ctx.saved_tensors[3:] or None, cs)
+        if grads is not None:      # a pair no head of this call uses gets no gradient from it
+            return (g, None, None, None, None) + tuple(t.to(dt) if t is not None else None for t, dt in zip(grads, dtypes))
+        return (g, None, None, None, None)
+
+
+class QKLayerNorm(nn.Module):
+    """q_norm / k_norm of Attention(qk_norm="ln"): nn.LayerNorm(dim_heads, elementwise_affine=True, eps=1e-6) of the reference
+    (transformer.py:375-376) — same parameter names (weight, bias), ones / zeros at construction, one set shared by all heads.
+    It has no forward of its own: the normalisation runs inside the attention's kernels, which read fp32 tables (_as_f32)."""
+
+    def __init__(self, dim, eps=1e-6):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(dim))
+        self.bias = nn.Parameter(torch.zeros(dim))
+        self.eps = eps
+        self._f32_cache = {}
+
+    def _as_f32(self, name):
+        """fp32, 16-byte aligned copy of a parameter for the kernels (LayerNorm._as_f32): the parameter itself when it already is both,
+        else a converted copy cached until the parameter changes (in-place version counter / storage / epoch)."""
+        t = getattr(self, name)
+        if t.dtype == torch.float32 and t.data_ptr() % 16 == 0 and t.is_contiguous():
+            return t.detach()
+        if not _caches.trackable(t):
+            return t.detach().float().clone()
+        key = (t.data_ptr(), _caches.version_of(t), t.device, _caches.epoch_of(t))
+        hit = self._f32_cache.get(name)
+        if hit is None or hit[0] != key:
+            hit = (key, t.detach().float().clone())
+            self._f32_cache[name] = hit
+        return hit[1]
 
 
 class _SwiGLUFn(torch.autograd.Function):
@@ -352,8 +470,12 @@ class Attention(nn.Module):
     def __init__(self, dim, dim_heads=64, dim_context=None, causal=False, zero_init_output=True, qk_norm="none",
                  differential=False, feat_scale=False):
         super().__init__()
-        if causal or qk_norm != "none" or differential or feat_scale:
-            raise NotImplementedError("causal / qk_norm / differential / feat_scale attention are not on the HIP path")
+        if causal or differential or feat_scale:
+            raise NotImplementedError("causal / differential / feat_scale attention are not on the HIP path")
+        if qk_norm not in ("l2", "ln", "dyt", "none"):
+            raise ValueError(f'qk_norm must be one of ["l2", "ln", "none"], got {qk_norm}')
+        if qk_norm == "dyt":
+            raise NotImplementedError('qk_norm="dyt" (DynamicTanh) is not on the HIP path; "ln" and "l2" are')
         if dim_heads != 64:
             raise NotImplementedError("the HIP attention kernel is specialised for head dim 64 (every Stable Audio DiT config)")
         self.dim, self.dim_heads = dim, dim_heads
@@ -368,12 +490,30 @@ class Attention(nn.Module):
         self.to_out = Linear(dim, dim, bias=False)
         if zero_init_output:
             nn.init.zeros_(self.to_out.weight)
+        self.qk_norm = qk_norm
+        if qk_norm == "ln":
+            self.q_norm = QKLayerNorm(dim_heads, eps=1.0e-6)
+            self.k_norm = QKLayerNorm(dim_heads, eps=1.0e-6)
         self.causal = False
         self.scale = dim_heads ** -0.5
 
+    def _norm(self):
+        """(mode, fp32 tables (q gamma, q beta, k gamma, k beta) or None) for the kernels, or None without qk_norm."""
+        if self.qk_norm == "none":
+            return None
+        if self.qk_norm == "l2":
+            return ("l2", None)
+        return ("ln", (self.q_norm._as_f32("weight"), self.q_norm._as_f32("bias"), self.k_norm._as_f32("weight"), self.k_norm._as_f32("bias")))
+
+    def _norm_params(self):
+        return (self.q_norm.weight, self.q_norm.bias, self.k_norm.weight, self.k_norm.bias) if self.qk_norm == "ln" else ()
+
     @staticmethod
-    def _heads(ops, lin, x2, cs, heads, nb, ntok, sec0, nsec, tag):
-        """Input projection straight into attention operand planes (bf16, or fp8 operands when the layer is switched to fp8)."""
+    def _heads(ops, lin, x2, cs, heads, nb, ntok, sec0, nsec, tag, norm=None):
+        """Input projection straight into attention operand planes (bf16, or fp8 operands when the layer is switched to fp8);
+        norm (Attention._norm): q / k heads normalised in the same epilogue."""
+        if norm is not None:      # (never fp8: Attention.forward refuses an fp8 input projection under qk_norm)
+            return ops.gemm_heads_bf16(x2, lin.lowp_weight(), cs, heads, nb, ntok, sec0, nsec, reuse=tag, qk_norm=norm[0], norm_tables=norm[1])
         if isinstance(x2, _linear.Fp8Rows):
             qw, sw = lin.fp8_weight()
             alpha, calpha = _linear.fp8_scales(None, sw)
@@ -401,6 +541,9 @@ class Attention(nn.Module):
             raise NotImplementedError("rotary on a separate-projection attention is never used by the DiT")
         kv_input = context if (cross and context is not None) else x
         first = self.to_q if cross else self.to_qkv
+        norm = self._norm()
+        if norm is not None and (isinstance(x, _linear.Fp8Rows) or first.fp8 or (cross and self.to_kv.fp8)):
+            raise NotImplementedError("qk_norm on an fp8 input projection: the fp8 heads GEMM has no norm epilogue (keep to_qkv / to_q / to_kv in bf16)")
         if not torch.is_grad_enabled() and _lowp(x, first.weight) and first.lowp_weight() is not None \
                 and (not cross or self.to_kv.lowp_weight() is not None):
             # inference, bf16: head split, rotary and the attention kernel's operand planes come straight out of the
@@ -413,20 +556,24 @@ class Attention(nn.Module):
                 x2 = x2 if x2.dtype == torch.bfloat16 else ops.cast_bf16(x2.contiguous())
             if cross:
                 m = kv_input.shape[1]
-                pq = self._heads(ops, self.to_q, x2, None, h, b, n, 0, 1, "cross")
+                pq = self._heads(ops, self.to_q, x2, None, h, b, n, 0, 1, "cross", norm)
                 # the conditioning is the same tensor at every sampler step (dit.py caches its embedding): its K / V planes are
                 # computed once per (context object, version, weight version) and kept in this layer's own buffers
                 w = self.to_kv.weight
                 can_cache = _caches.trackable(kv_input, w)    # an inference tensor carries no version counter: project it every call
                 key = (_caches.version_of(kv_input), _caches.version_of(w), w.data_ptr(), _caches.epoch_of(w), bool(self.to_kv.fp8),
                        tuple(kv_input.shape), kv_input.dtype)
+                if self.qk_norm == "ln":     # the K planes hold k_norm's output: a changed norm parameter must not keep them
+                    kw, kb = self.k_norm.weight, self.k_norm.bias
+                    can_cache = can_cache and _caches.trackable(kw, kb)
+                    key += (_caches.version_of(kw), kw.data_ptr(), _caches.version_of(kb), kb.data_ptr(), _caches.epoch_of(kw, kb))
                 hit = can_cache and getattr(self, "_kv_ctx", None) is kv_input and self._kv_key == key
                 if hit:
                     pkv = self._kv_planes
                 else:
                     c2 = kv_input.reshape(b * m, -1)
                     c2 = c2 if c2.dtype == torch.bfloat16 else ops.cast_bf16(c2.contiguous())
-                    pkv = self._heads(ops, self.to_kv, c2, None, kv_h, b, m, 1, 2, ("crosskv", id(self)))
+                    pkv = self._heads(ops, self.to_kv, c2, None, kv_h, b, m, 1, 2, ("crosskv", id(self)), norm)
                     if can_cache:
                         self._kv_ctx, self._kv_key, self._kv_planes = kv_input, key, pkv
                     else:
@@ -434,24 +581,30 @@ class Attention(nn.Module):
                 out = ops.attention_planes(pq["q"], pkv["k"], pkv["v_tr"], n, m, self.scale)
             else:
                 cs = rotary_pos_emb[0] if rotary_pos_emb is not None else None
-                pl = self._heads(ops, self.to_qkv, x2, cs, h, b, n, 0, 3, "self")
+                pl = self._heads(ops, self.to_qkv, x2, cs, h, b, n, 0, 3, "self", norm)
                 out = ops.attention_planes(pl["q"], pl["k"], pl["v_tr"], n, n, self.scale)
             return self.to_out(out, res=res)
         if _ops().train_fused_nodes and dh == 64:
             if cross:
-                out = _CrossAttnFn.apply(self.to_q(x), self.to_kv(kv_input), h, kv_h, dh, self.scale)
+                out = _CrossAttnFn.apply(self.to_q(x), self.to_kv(kv_input), h, kv_h, dh, self.scale, norm, *self._norm_params())
             else:
                 cs = rotary_pos_emb[0] if rotary_pos_emb is not None else None
-                out = _SelfAttnFn.apply(self.to_qkv(x), cs, h, dh, self.scale)     # (B, N, H*dh): heads already merged
+                out = _SelfAttnFn.apply(self.to_qkv(x), cs, h, dh, self.scale, norm, *self._norm_params())     # (B, N, H*dh): heads already merged
             return self.to_out(out, res=res)
         if cross:
-            q = self.to_q(x).view(b, n, h, dh).permute(0, 2, 1, 3)
+            q2 = self.to_q(x)
             kv = self.to_kv(kv_input)
+            if norm is not None:
+                q2 = _QKNormFn.apply(q2, None, h, h, norm, *self._norm_params())
+                kv = _QKNormFn.apply(kv, None, kv_h, 0, norm, *self._norm_params())
+            q = q2.view(b, n, h, dh).permute(0, 2, 1, 3)
             k = kv[..., :kv_h * dh].unflatten(-1, (kv_h, dh)).permute(0, 2, 1, 3)
             v = kv[..., kv_h * dh:].unflatten(-1, (kv_h, dh)).permute(0, 2, 1, 3)
         else:
             qkv = self.to_qkv(x)
-            if rotary_pos_emb is not None:
+            if norm is not None:
+                qkv = _QKNormFn.apply(qkv, rotary_pos_emb[0] if rotary_pos_emb is not None else None, 2 * h, h, norm, *self._norm_params())
+            elif rotary_pos_emb is not None:
                 cs, _ = rotary_pos_emb
                 qkv = _RopeQKFn.apply(qkv, cs, h, dh)
             hd = h * dh
