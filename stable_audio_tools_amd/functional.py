@@ -17,7 +17,6 @@ recompute the worse trade on MI355X.
 """
 import torch
 
-from . import _caches
 from . import ops as _ops_mod
 from .ops import PACK_CONV_DGRAD, PACK_CONV_FWD, PACK_POLYPHASE
 
@@ -361,14 +360,12 @@ class ResidualUnitFn(torch.autograd.Function):
         # the k1 data-gradient also writes dh as the planes its consumer — the k7 data-gradient two launches below — reads
         want_emit = ops.emit_ok(w1.shape[0], k2, 1, t, dil) and ops.k7q_applicable(w1.shape[0], k1, 1, dil, pad1, c)
         # the k7 weight gradient from planes (csrc/conv_wgrad7_planes.h): dh's, emitted below, and the ones the forward conv read — if they
-        # are still what it read (same x, same parameters, the owned buffer not rewritten since); anything else keeps the fp32 kernel
+        # are still what it read (ops.kept_planes_valid); anything else keeps the fp32 kernel
         kp = getattr(ctx, "k7_planes", None)
         bsz = dy.shape[0]
         skip_dh = False
-        if kp is not None and not (ops.wgrad7_planes and not ctx.recompute and want_emit and k1 == 7 and w1.shape[0] == c
-                                   and kp["gen"] == kp["buf"]["gen"] and kp["ptr"] == x.data_ptr() and kp["shape"] == tuple(x.shape)
-                                   and kp["ver"] == _caches.version_of(x) and kp["snake"] == ops._snake_key((a1, b1))
-                                   and ops.conv_wgrad7_planes_ok(bsz, c, c, t, dil, pad1, kp["buf"]["rows"], kp["buf"]["rows"])):
+        if kp is not None and not (not ctx.recompute and want_emit and k1 == 7 and w1.shape[0] == c
+                                   and ops.kept_planes_valid(kp, x, (a1, b1), dil, pad1)):
             kp = None
 
         def wgrad1(dh, bias_grad):

@@ -61,12 +61,31 @@ class SatOps:
     def __init__(self, cdll):
         self.lib = cdll
         self.simulator = bool(cdll.sat_is_simulator())
+        # every piece of mutable state of the object (release_workspaces / release_owned_planes empty it again)
+        self._planes = {}           # _workspace: key -> cached tensor
+        self._own_planes = {}       # _owned_planes: the plane buffers the k7 convs own
+        self._emitted = None        # _note_emitted: the planes a producer wrote for the conv that reads its output next
+        self._dh_unwritten = None   # ru_k1_bwd(skip_dh=True): address of the dh that exists only as planes
+        self._zpage = None          # _zeros_page
+        self._disc_pool, self._disc_gen, self._disc_geoms = {}, {}, {}      # _disc_plane_buf / disc_geom
+        self._disc_emitted = None   # disc_register
 
     # ------------------------------------------------------------------ plumbing
     def _stream(self, t):
         if self.simulator:
             return None
         return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    def _workspace(self, key, shape, dtype, device, zero=False, grow=False):
+        """The tensor cached under `key`: a workspace that outlives the call and keeps its address from one call to the next (a HIP-graph
+        replay depends on that).  Allocated on first use — zero-filled ONCE (zero=True: buffers whose writers leave the padding alone) or
+        uninitialised — and reused while it is on `device` with exactly `shape`; grow=True (`shape`: an element count): while it holds
+        at least that many elements (the largest size seen)."""
+        shape = (shape,) if isinstance(shape, int) else tuple(shape)
+        ws = self._planes.get(key)
+        if ws is None or ws.device != device or (ws.numel() < shape[0] if grow else tuple(ws.shape) != shape):
+            ws = self._planes[key] = (_keep_zeros if zero else _keep_empty)(shape, dtype, device)
+        return ws
 
     def _chk(self, status):
         if status != 0:
@@ -151,6 +170,19 @@ class SatOps:
         c, r = partial.shape
         return self.rowsum(partial.view(1, c, r))
 
+    def _dsnake_args(self, dsnake, cout, rows, device):
+        """dsnake = (x2, log-alpha2, log-beta2) | None -> (x2, a2, b2, pda, pdb): the kernel's arguments for the snake data-gradient
+        epilogue, pda / pdb the (cout, rows) partial sums of d log-alpha2 / d log-beta2 (halves of one buffer: _sum_pair)."""
+        if dsnake is None:
+            return None, None, None, None, None
+        x2, a2, b2 = dsnake
+        self._f32(x2, a2, b2)
+        return (x2, a2, b2, *torch.empty(2, cout, rows, dtype=torch.float32, device=device).unbind(0))
+
+    def _dsnake_result(self, y, pda, pdb):
+        """y, or with dsnake (y, d log-alpha2, d log-beta2)."""
+        return y if pda is None else (y, *self._sum_pair(pda, pdb))
+
     def conv1d(self, x, w_packed, cout, k, stride=1, dil=1, pad=0, tout=None, bias=None, snake=None, res=None,
                tanh_out=False, dsnake=None, out=None):
         """y = conv(snake(x)) [+bias] [+res] ; or, with dsnake=(x2, alpha2, beta2):
@@ -161,19 +193,12 @@ class SatOps:
         alpha, beta = snake if snake is not None else (None, None)
         self._f32(x, w_packed, bias, alpha, beta, res)
         y = self._conv_out(out, b, cout, tout, x.device)
-        x2 = a2 = b2 = pda = pdb = None
-        rows = 0
-        if dsnake is not None:
-            x2, a2, b2 = dsnake
-            self._f32(x2, a2, b2)
-            rows = self.lib.sat_conv1d_partial_rows(b, tout)
-            pda, pdb = torch.empty(2, cout, rows, dtype=torch.float32, device=x.device).unbind(0)
+        rows = self.lib.sat_conv1d_partial_rows(b, tout) if dsnake is not None else 0
+        x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, rows, x.device)
         self._chk(self.lib.sat_conv1d(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(alpha), _ptr(beta), _ptr(res), _ptr(y),
                                       _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb),
                                       b, cin, cout, tin, tout, k, stride, dil, pad, int(tanh_out), self._stream(x)))
-        if dsnake is not None:
-            return (y, *self._sum_pair(pda, pdb))
-        return y
+        return self._dsnake_result(y, pda, pdb)
 
     # -- bf16x3 split-MFMA path (csrc/conv1d_bf16x3.hip): stride-1 convs with K <= 8, and the K == 2*stride
     #    down / up (transposed) convs with a power-of-two stride --
@@ -196,28 +221,15 @@ class SatOps:
         alpha, beta = snake if snake is not None else (None, None)
         self._f32(x, w, bias, alpha, beta)
         y = torch.empty(b, cout, t, dtype=torch.float32, device=x.device)
-        x2 = a2 = b2 = pda = pdb = None
-        if dsnake is not None:
-            x2, a2, b2 = dsnake
-            self._f32(x2, a2, b2)
-            rows = self.lib.sat_edge_conv_partial_rows(b, t)
-            pda, pdb = torch.empty(2, cout, rows, dtype=torch.float32, device=x.device).unbind(0)
-        ehi = elo = ela = elb = None
-        erows = 0
-        if emit is not None:      # emit = {"snake": (la, lb) | None}: act_next(y) as the planes of the k7 conv that reads y next (narrow-input form)
-            esnake = emit.get("snake")
-            if esnake is not None:
-                ela, elb = esnake
-                self._f32(ela, elb)
-            ehi, elo, erows = self._emit_planes(b, cout, t, x.device, self._stream(x), owner=esnake)
+        rows = self.lib.sat_edge_conv_partial_rows(b, t) if dsnake is not None else 0
+        x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, rows, x.device)
+        # emit: act_next(y) as the planes of the k7 conv that reads y next (narrow-input form); this kernel takes the log-parameters themselves
+        ehi, elo, ela, elb, erows = self._emit_args(emit, b, cout, t, x.device, self._stream(x), consts=False)
         self._chk(self.lib.sat_edge_conv(_ptr(x), _ptr(w), _ptr(bias), _ptr(alpha), _ptr(beta), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2),
                                          _ptr(pda), _ptr(pdb), _ptr(ehi), _ptr(elo), _ptr(ela), _ptr(elb), erows, b, cin, cout, t, k, pad, mode,
                                          int(tanh_out), self._stream(x)))
-        if emit is not None:
-            self._note_emitted(y, emit.get("snake"), ehi, elo, erows)
-        if dsnake is not None:
-            return (y, *self._sum_pair(pda, pdb))
-        return y
+        self._emit_done(emit, y, ehi, elo, erows)
+        return self._dsnake_result(y, pda, pdb)
 
     def edge_conv_wgrad(self, dy, x, k, pad, snake=None, dy_rowsum=False, raw=False):
         """dW (M, N, K) of conv1d(snake(x), W) with <= 2 channels on one side; contract of conv_wgrad7_bf16x3 (raw: WgradSlabs + the bias
@@ -232,13 +244,18 @@ class SatOps:
         rs = torch.empty(m, nsplit, dtype=torch.float32, device=dy.device) if fused else None
         self._chk(self.lib.sat_edge_conv_wgrad(_ptr(dy), _ptr(x), _ptr(alpha), _ptr(beta), _ptr(partial), _ptr(rs), b, m, n, t, k, pad,
                                                self._stream(dy)))
-        slabs = WgradSlabs(partial, nsplit, (m, n, k), (n * k, k, 1))
+        return self._wgrad_result(WgradSlabs(partial, nsplit, (m, n, k), (n * k, k, 1)), raw, dy, dy_rowsum, rs)
+
+    def _wgrad_result(self, slabs, raw, dy, dy_rowsum, rs):
+        """What a weight-gradient wrapper returns: dW — the slabs themselves with raw, else their sum — and with dy_rowsum the bias
+        gradient too: from rs (M, nsplit), the row sums the kernel made on the way, or else from dy; raw leaves it one reduction short
+        of done, (M, R), for wn_grad_splits to finish."""
         dw = slabs if raw else slabs.reduce(self)
         if not dy_rowsum:
             return dw
         if raw:
-            return dw, (rs if fused else self.rowsum(dy, partial=True))
-        return dw, (self._sum_last(rs) if fused else self.rowsum(dy))
+            return dw, (rs if rs is not None else self.rowsum(dy, partial=True))
+        return dw, (self._sum_last(rs) if rs is not None else self.rowsum(dy))
 
     def bf16x3_ok(self, k, stride, dil, transposed=False):
         if not self.use_bf16x3:
@@ -272,16 +289,12 @@ class SatOps:
         """w: (D0, D1, K) fp32 -> (hi, lo) int16 planes.  mode 0: conv weight [out][in][K]; mode 1: data-gradient of a
         stride-1 conv; mode 2: transposed-conv weight [in][out][K].  q=True (stride 1, 5 <= K <= 7, modes 0 / 1): the layout of
         the k7q kernel (sat_pack_weights_k7q) — returned as (hi, lo, "q") so that conv1d_bf16x3 routes to it."""
+        if q:
+            if stride != 1:
+                raise RuntimeError("sat_pack_weights_k7q: unsupported shape")
+            return (*self.pack_k7q(w, mode), "q")
         self._f32(w)
         d0, d1, k = w.shape
-        if q:
-            n = self.lib.sat_pack_weights_k7q_size(d0, d1, k, mode)
-            if n <= 0 or stride != 1:
-                raise RuntimeError("sat_pack_weights_k7q: unsupported shape")
-            hi = torch.empty(n, dtype=torch.int16, device=w.device)
-            lo = torch.empty(n, dtype=torch.int16, device=w.device)
-            self._chk(self.lib.sat_pack_weights_k7q(_ptr(w), _ptr(hi), _ptr(lo), d0, d1, k, mode, self._stream(w)))
-            return hi, lo, "q"
         n = self.lib.sat_pack_weights_bf16x3_size(d0, d1, k, stride, mode)
         if n <= 0:
             raise RuntimeError("sat_pack_weights_bf16x3: unsupported shape")
@@ -314,32 +327,18 @@ class SatOps:
         if snake is not None:
             sa, sib = sconsts if sconsts is not None else self.snake_consts(snake[0], snake[1])
         y = self._conv_out(out, b, cout, tout, x.device)
-        x2 = a2 = b2 = pda = pdb = None
-        if dsnake is not None:
-            x2, a2, b2 = dsnake
-            self._f32(x2, a2, b2)
-            pda, pdb = torch.empty(2, cout, rows, dtype=torch.float32, device=x.device).unbind(0)
+        x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, rows, x.device)
+        ehi, elo, ea, eib, erows = self._emit_args(emit, b, cout, tout, x.device, self._stream(x))
+        args = (_ptr(x), _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(sa), _ptr(sib),
+                _ptr(res), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb),
+                b, cin, cout, tin, tout, *dims, int(tanh_out))
         if emit is not None:
             # plane emission (sat_conv1d_bf16x3_emit): the planes the k7 conv that consumes y next would otherwise build in a pre-pass
-            esnake = emit.get("snake")
-            ea = eib = None
-            if esnake is not None:
-                ea, eib = self.snake_consts(esnake[0], esnake[1])
-            ehi, elo, erows = self._emit_planes(b, cout, tout, x.device, self._stream(x), owner=esnake)
-            self._chk(self.lib.sat_conv1d_bf16x3_emit(_ptr(x), _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(sa), _ptr(sib),
-                                                      _ptr(res), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb),
-                                                      b, cin, cout, tin, tout, *dims, int(tanh_out), _ptr(ehi), _ptr(elo), _ptr(ea), _ptr(eib),
-                                                      erows, self._stream(x)))
-            self._note_emitted(y, esnake, ehi, elo, erows)
-            if dsnake is not None:
-                return (y, *self._sum_pair(pda, pdb))
-            return y
-        self._chk(fn(_ptr(x), _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(sa), _ptr(sib),
-                     _ptr(res), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb),
-                     b, cin, cout, tin, tout, *dims, int(tanh_out), self._stream(x)))
-        if dsnake is not None:
-            return (y, *self._sum_pair(pda, pdb))
-        return y
+            self._chk(self.lib.sat_conv1d_bf16x3_emit(*args, _ptr(ehi), _ptr(elo), _ptr(ea), _ptr(eib), erows, self._stream(x)))
+        else:
+            self._chk(fn(*args, self._stream(x)))
+        self._emit_done(emit, y, ehi, elo, erows)
+        return self._dsnake_result(y, pda, pdb)
 
     # ---- fused ResidualUnit forward (csrc/conv1d_bf16x3_k7q.h, FUSED): one launch for snake -> conv7 -> snake -> conv1 -> + x ----
     ru_fused = True
@@ -371,38 +370,31 @@ class SatOps:
         sa1, sib1 = sconsts[0] if sconsts is not None else self.snake_consts(snake1[0], snake1[1])
         sa2, sib2 = sconsts[1] if sconsts is not None else self.snake_consts(snake2[0], snake2[1])
         em = self._take_emitted(x, snake1)
-        if em is not None:
-            hi, lo, rows = em["hi"], em["lo"], em["rows"]
-        else:
-            rows = self.lib.sat_conv1d_k7_plane_rows(t, t, pad)
-            c8 = (c + 7) // 8
-            need = 2 * b * c8 * rows * 8
-            wkey = ("k7p", x.device, st.value if st is not None else 0)
-            ws = self.__dict__.setdefault("_planes", {}).get(wkey)
-            if ws is None or ws.numel() < need:
-                ws = _keep_empty(need, torch.int16, x.device)
-                self._planes[wkey] = ws
-            hi, lo = ws[:need // 2], ws[need // 2:need]
-            self._chk(self.lib.sat_conv1d_k7_planes(_ptr(x), _ptr(sa1), _ptr(sib1), _ptr(hi), _ptr(lo), b, c, t, rows, st))
+        hi, lo, rows = (em["hi"], em["lo"], em["rows"]) if em is not None else self._k7_prepass(x, sa1, sib1, t, pad, st)
         h = torch.empty_like(x) if keep_h else None
         y = torch.empty_like(x)
-        ehi = elo = ea = eib = None
-        erows = 0
-        if emit is not None:
-            esnake = emit.get("snake")
-            if esnake is not None:
-                ea, eib = self.snake_consts(esnake[0], esnake[1])
-            ehi, elo, erows = self._emit_planes(b, c, t, x.device, st)
-            if ehi.data_ptr() == hi.data_ptr():
-                # the input planes ARE this shape's emission target (written by the previous unit): a workgroup reads halo rows its
-                # neighbours' tiles would overwrite -> emit into a second buffer and alternate
-                ehi, elo, erows = self._emit_planes(b, c, t, x.device, st, alt=True)
+        ehi, elo, ea, eib, erows = self._emit_args(emit, b, c, t, x.device, st, owned=False)
+        if emit is not None and ehi.data_ptr() == hi.data_ptr():
+            # the input planes ARE this shape's emission target (written by the previous unit): a workgroup reads halo rows its
+            # neighbours' tiles would overwrite -> emit into a second buffer and alternate
+            ehi, elo, erows = self._emit_planes(b, c, t, x.device, st, alt=True)
         self._chk(self.lib.sat_residual_unit_fwd(_ptr(hi), _ptr(lo), rows, _ptr(w7q[0]), _ptr(w7q[1]), _ptr(bias1), _ptr(sa2), _ptr(sib2),
                                                  _ptr(w1q[0]), _ptr(w1q[1]), _ptr(bias2), _ptr(x), _ptr(h), _ptr(y), b, c, t, k, dil, pad,
                                                  _ptr(ehi), _ptr(elo), _ptr(ea), _ptr(eib), erows, st))
-        if emit is not None:
-            self._note_emitted(y, emit.get("snake"), ehi, elo, erows)
+        self._emit_done(emit, y, ehi, elo, erows)
         return h, y
+
+    def _k7_prepass(self, x, sa, sib, tout, pad, st):
+        """act(x) as the bf16 hi / lo planes a k7 conv (tout, pad) reads, by one conversion pass (sat_conv1d_k7_planes) into the shared
+        workspace — one per (device, stream), of the largest size seen: the pass and its conv are enqueued back to back on the caller's
+        current stream.  Returns (hi, lo, rows)."""
+        b, c, t = x.shape
+        rows = self.lib.sat_conv1d_k7_plane_rows(t, tout, pad)
+        need = 2 * b * ((c + 7) // 8) * rows * 8
+        ws = self._workspace(("k7p", x.device, st.value if st is not None else 0), need, torch.int16, x.device, grow=True)
+        hi, lo = ws[:need // 2], ws[need // 2:need]
+        self._chk(self.lib.sat_conv1d_k7_planes(_ptr(x), _ptr(sa), _ptr(sib), _ptr(hi), _ptr(lo), b, c, t, rows, st))
+        return hi, lo, rows
 
     # ---- plane emission bookkeeping: producer -> the ONE k7 conv that consumes its output next ----
     k7_emit = True
@@ -420,6 +412,26 @@ class SatOps:
             return
         self._emitted = {"ptr": y.data_ptr(), "shape": tuple(y.shape), "ver": _caches.version_of(y), "snake": self._snake_key(snake),
                          "hi": hi, "lo": lo, "rows": rows}
+
+    def _emit_args(self, emit, b, c, t, device, st, consts=True, owned=True):
+        """emit = {"snake": (la, lb) | None} | None -> (hi, lo, a, b, rows): the planes the producer's epilogue writes act_next(y) into
+        for a (b, c, t) output y, and act_next's parameters as the kernel wants them: its constants (snake_consts), or with consts=False
+        the log-parameters as they are.  owned=False: the shared per-shape pair even where the consumer owns a buffer (the fused unit)."""
+        if emit is None:
+            return None, None, None, None, 0
+        esnake = emit.get("snake")
+        ea = eb = None
+        if esnake is not None and consts:
+            ea, eb = self.snake_consts(esnake[0], esnake[1])
+        elif esnake is not None:
+            ea, eb = esnake
+            self._f32(ea, eb)
+        hi, lo, rows = self._emit_planes(b, c, t, device, st, owner=esnake if owned else None)
+        return hi, lo, ea, eb, rows
+
+    def _emit_done(self, emit, y, hi, lo, rows):
+        if emit is not None:
+            self._note_emitted(y, emit.get("snake"), hi, lo, rows)
 
     def emit_ok(self, cout, k, stride, tout, consumer_dil):
         """May the conv (k, stride) producing (B, cout, tout) emit planes for a k7 conv of dilation consumer_dil that reads it next?"""
@@ -454,7 +466,7 @@ class SatOps:
         if snake is None or not self.wgrad7_planes:
             return None
         key = (snake[0].data_ptr(), snake[1].data_ptr(), b, c, t, device)
-        cache = self.__dict__.setdefault("_own_planes", {})
+        cache = self._own_planes
         own = cache.get(key)
         capturing = device.type == "cuda" and torch.cuda.is_current_stream_capturing()
         sv = st.value if st is not None else 0
@@ -484,32 +496,23 @@ class SatOps:
             return own["hi"], own["lo"], own["rows"]
         rows = self.lib.sat_conv1d_k7_plane_rows(t, t, 0)          # pad 0 needs the most rows: valid for every consumer padding
         key = ("emit", b, c, t, device, st.value if st is not None else 0, alt)
-        cache = self.__dict__.setdefault("_planes", {})
-        pl = cache.get(key)
-        if pl is None:
-            n = b * ((c + 7) // 8) * rows * 8
-            pl = (_keep_zeros(n, torch.int16, device), _keep_zeros(n, torch.int16, device), rows)
-            cache[key] = pl
-        return pl
-
-    def _take_emitted(self, x, snake):
-        """Planes a producer emitted for exactly this tensor and activation (consumed once), or None."""
-        e = self.__dict__.get("_emitted")
-        if e is None:
-            return None
-        self._emitted = None
-        if (e["ptr"] == x.data_ptr() and e["shape"] == tuple(x.shape) and _caches.trackable(x) and e["ver"] == _caches.version_of(x)
-                and e["snake"] == self._snake_key(snake)):
-            return e
-        return None
+        n = b * ((c + 7) // 8) * rows * 8
+        return (self._workspace(key + ("hi",), n, torch.int16, device, zero=True),
+                self._workspace(key + ("lo",), n, torch.int16, device, zero=True), rows)
 
     def _peek_emitted(self, x, snake):
-        """_take_emitted without consuming: the planes stay for the conv that takes them next."""
-        e = self.__dict__.get("_emitted")
+        """Planes a producer emitted for exactly this tensor and activation, or None; they stay for the conv that takes them next."""
+        e = self._emitted
         if (e is not None and e["ptr"] == x.data_ptr() and e["shape"] == tuple(x.shape) and _caches.trackable(x)
                 and e["ver"] == _caches.version_of(x) and e["snake"] == self._snake_key(snake)):
             return e
         return None
+
+    def _take_emitted(self, x, snake):
+        """_peek_emitted, consuming: whatever was emitted is gone afterwards, taken or not."""
+        e = self._peek_emitted(x, snake)
+        self._emitted = None
+        return e
 
     def conv1d_bf16x3(self, x, w_planes, cout, k, stride=1, dil=1, pad=0, tout=None, bias=None, snake=None, res=None,
                       tanh_out=False, dsnake=None, out=None, sconsts=None, emit=None, keep_planes=None):
@@ -528,9 +531,7 @@ class SatOps:
                                  bias, snake, res, tanh_out, dsnake, out, sconsts, emit)
 
     # the k = 7 convs of the ResidualUnits read their (activated) input as pre-split bf16 planes: written by the producer's epilogue
-    # (plane emission) or by one conversion pass per conv (sat_conv1d_k7_planes) instead of one per workgroup.  The two planes live in
-    # a cached workspace of the largest size seen, one per (device, stream): the pre-pass and its conv are enqueued back to back on
-    # the caller's current stream.
+    # (plane emission) or by one conversion pass per conv (_k7_prepass) instead of one per workgroup.
     def _k7_planes_call(self, prows, x, w_planes, cout, tout, k, dil, pad, bias, snake, res, tanh_out, dsnake, out=None, sconsts=None,
                         keep_planes=None):
         b, cin, tin = x.shape
@@ -556,31 +557,14 @@ class SatOps:
                              "snake": self._snake_key(snake)}
         if em is not None:
             hi, lo, rows = em["hi"], em["lo"], em["rows"]          # the producer's epilogue already wrote act(x) as planes
-        elif own is not None:
-            pass
-        else:
-            rows = self.lib.sat_conv1d_k7_plane_rows(tin, tout, pad)
-            c8 = (cin + 7) // 8
-            need = 2 * b * c8 * rows * 8
-            wkey = ("k7p", x.device, st.value if st is not None else 0)       # one workspace per (device, stream)
-            ws = self.__dict__.setdefault("_planes", {}).get(wkey)
-            if ws is None or ws.numel() < need:
-                ws = _keep_empty(need, torch.int16, x.device)
-                self._planes[wkey] = ws
-            hi, lo = ws[:need // 2], ws[need // 2:need]
-            self._chk(self.lib.sat_conv1d_k7_planes(_ptr(x), _ptr(sa), _ptr(sib), _ptr(hi), _ptr(lo), b, cin, tin, rows, st))
+        elif own is None:
+            hi, lo, rows = self._k7_prepass(x, sa, sib, tout, pad, st)
         y = self._conv_out(out, b, cout, tout, x.device)
-        x2 = a2 = b2 = pda = pdb = None
-        if dsnake is not None:
-            x2, a2, b2 = dsnake
-            self._f32(x2, a2, b2)
-            pda, pdb = torch.empty(2, cout, prows, dtype=torch.float32, device=x.device).unbind(0)
+        x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, prows, x.device)
         self._chk(self.lib.sat_conv1d_bf16x3_planesq(_ptr(hi), _ptr(lo), rows, _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(res),
                                                      _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb), b, cin, cout, tin, tout,
                                                      k, dil, pad, int(tanh_out), {True: 0, False: 1, "force": 2}[self.k7q_persist] | (4 if self.k7q_dma_in_mfma else 0), st))
-        if dsnake is not None:
-            return (y, *self._sum_pair(pda, pdb))
-        return y
+        return self._dsnake_result(y, pda, pdb)
 
     def convtr1d_bf16x3(self, x, w_planes, cout, k, stride, pad, tout=None, bias=None, snake=None, res=None,
                         tanh_out=False, dsnake=None, sconsts=None):
@@ -600,21 +584,14 @@ class SatOps:
         alpha, beta = snake if snake is not None else (None, None)
         self._f32(x, w_packed, bias, alpha, beta, res)
         y = torch.empty(b, cout, tout, dtype=torch.float32, device=x.device)
-        x2 = a2 = b2 = pda = pdb = None
-        rows = 0
-        if dsnake is not None:
-            x2, a2, b2 = dsnake
-            self._f32(x2, a2, b2)
-            rows = self.lib.sat_convtr1d_partial_rows(b, tout, stride, pad)
-            if rows < 0:
-                raise RuntimeError("sat_convtr1d: unsupported stride")
-            pda, pdb = torch.empty(2, cout, rows, dtype=torch.float32, device=x.device).unbind(0)
+        rows = self.lib.sat_convtr1d_partial_rows(b, tout, stride, pad) if dsnake is not None else 0
+        if rows < 0:
+            raise RuntimeError("sat_convtr1d: unsupported stride")
+        x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, rows, x.device)
         self._chk(self.lib.sat_convtr1d(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(alpha), _ptr(beta), _ptr(res), _ptr(y),
                                         _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb),
                                         b, cin, cout, tin, tout, k, stride, pad, int(tanh_out), self._stream(x)))
-        if dsnake is not None:
-            return (y, *self._sum_pair(pda, pdb))
-        return y
+        return self._dsnake_result(y, pda, pdb)
 
     def conv_wgrad(self, lo, hi, k, stride=1, dil=1, pad=0, snake=None, snake_on=0, lo_rowsum=False, raw=False):
         """dW[m][n][k] = sum_{b,t} actA(lo[b,m,t]) * actB(hi[b,n,t*s + k*d - pad]), (M, N, K).
@@ -644,13 +621,7 @@ class SatOps:
             self._chk(self.lib.sat_conv_wgrad(_ptr(lo), _ptr(hi), _ptr(alpha), _ptr(beta), snake_on if snake is not None else 0,
                                               _ptr(partial), so_m, so_n, so_k, bsz, m, n, tlo, thi, k, stride, dil, pad,
                                               self._stream(lo)))
-        slabs = WgradSlabs(partial, nsplit, (m, n, k), (so_m, so_n, so_k))
-        dw = slabs if raw else slabs.reduce(self)
-        if not lo_rowsum:
-            return dw
-        if raw:
-            return dw, (rs if rs is not None else self.rowsum(lo, partial=True))
-        return dw, (self._sum_last(rs) if rs is not None else self.rowsum(lo))
+        return self._wgrad_result(WgradSlabs(partial, nsplit, (m, n, k), (so_m, so_n, so_k)), raw, lo, lo_rowsum, rs)
 
     # ---- fused backward of a ResidualUnit's 1x1 conv (csrc/ru_k1_bwd.hip): one pass over dy and h ----
     ru_k1_fused = True
@@ -721,17 +692,11 @@ class SatOps:
         rs = torch.empty(m, nsplit, dtype=torch.float32, device=dy.device) if fused else None
         self._chk(self.lib.sat_conv_wgrad7_bf16x3(_ptr(dy), _ptr(x), _ptr(alpha), _ptr(beta), _ptr(partial), n, 1, m * n,
                                                   b, m, n, t, dil, pad, _ptr(rs), self._stream(dy)))
-        slabs = WgradSlabs(partial, nsplit, (m, n, 7), (n, 1, m * n))
-        dw = slabs if raw else slabs.reduce(self)
-        if not dy_rowsum:
-            return dw
-        if raw:         # the bias gradient one reduction short of done: wn_grad_splits finishes it
-            return dw, (rs if fused else self.rowsum(dy, partial=True))
-        return dw, (self._sum_last(rs) if fused else self.rowsum(dy))
+        return self._wgrad_result(WgradSlabs(partial, nsplit, (m, n, 7), (n, 1, m * n)), raw, dy, dy_rowsum, rs)
 
     def _check_written(self, t):
         """A dh whose fp32 store ru_k1_bwd(skip_dh=True) skipped exists only as planes: reading it as fp32 is a bug, not a fallback."""
-        if t is not None and self.__dict__.get("_dh_unwritten") is not None and t.data_ptr() == self._dh_unwritten:
+        if t is not None and self._dh_unwritten is not None and t.data_ptr() == self._dh_unwritten:
             raise RuntimeError("this tensor is a dh that sat_ru_k1_bwd did not write (skip_dh): only its planes exist")
 
     def dh_written(self):
@@ -742,10 +707,19 @@ class SatOps:
         """Drop every plane buffer a k7 conv owns (wgrad7_planes): after a model is discarded or reloaded, or before a pass at another
         input length.  The next training step re-creates what it needs (its first backward takes the fp32 weight-gradient kernel where
         the planes were emitted before the buffer existed).  Not while a captured graph that uses them may still be replayed."""
-        self.__dict__.pop("_own_planes", None)
+        self._own_planes.clear()
 
     def conv_wgrad7_planes_ok(self, b, m, n, t, dil, pad, rows_dy, rows_act):
         return self.use_bf16x3 and self.wgrad7_planes and self.lib.sat_conv_wgrad7_planes_ok(b, m, n, t, dil, pad, rows_dy, rows_act) == 1
+
+    def kept_planes_valid(self, kp, x, snake, dil, pad):
+        """Are the planes a k7 C -> C conv kept for its backward (kp = keep_planes["kept"], _k7_planes_call) still what its forward read —
+        the owned buffer not rewritten since, the same x (storage, shape, version), the same parameters — and does the planes
+        weight-gradient kernel serve the shape?  Anything else keeps the fp32 kernel."""
+        b, c, t = x.shape
+        return bool(self.wgrad7_planes and kp["gen"] == kp["buf"]["gen"] and kp["ptr"] == x.data_ptr() and kp["shape"] == tuple(x.shape)
+                    and kp["ver"] == _caches.version_of(x) and kp["snake"] == self._snake_key(snake)
+                    and self.conv_wgrad7_planes_ok(b, c, c, t, dil, pad, kp["buf"]["rows"], kp["buf"]["rows"]))
 
     def conv_wgrad7_planes(self, dy_planes, act_planes, b, m, n, t, dil, pad, raw=False):
         """dW (Cout, Cin, 7) as conv_wgrad7_bf16x3, both operands as (hi, lo, rows) planes: dy's and act(x)'s (sat_conv1d_k7_planes layout)."""
@@ -872,10 +846,8 @@ class SatOps:
     def release_workspaces(self):
         """Drop the cached plane / emission buffers (they are per activation shape and re-created, zero-filled, on demand): call after a
         run at a batch size or length that will not come back, before torch.cuda.empty_cache()."""
-        for name in ("_planes", "_own_planes", "_disc_pool", "_disc_gen", "_disc_geoms"):
-            d = self.__dict__.get(name)
-            if d is not None:
-                d.clear()
+        for d in (self._planes, self._own_planes, self._disc_pool, self._disc_gen, self._disc_geoms):
+            d.clear()
         self._emitted = None
         self._disc_emitted = None
 
@@ -883,7 +855,7 @@ class SatOps:
     def disc_geom(self, frames, w):
         """(P, L, lead, rows) of the pitched sequence / planes of a (.., frames, w) activation (sat_disc_geom)."""
         key = ("disc_geom", frames, w)
-        cache = self.__dict__.setdefault("_disc_geoms", {})
+        cache = self._disc_geoms
         g = cache.get(key)
         if g is None:
             out = [ctypes.c_int() for _ in range(4)]
@@ -900,9 +872,8 @@ class SatOps:
         c8 = (c + 7) // 8
         n = b * c8 * rows * 8
         key = (device, 0 if c8 == 1 else 1, slot)
-        gen = self.__dict__.setdefault("_disc_gen", {})
-        gen[key] = gen.get(key, 0) + 1                              # every request is a write: invalidates earlier registrations
-        pool = self.__dict__.setdefault("_disc_pool", {})
+        self._disc_gen[key] = self._disc_gen.get(key, 0) + 1        # every request is a write: invalidates earlier registrations
+        pool = self._disc_pool
         e = pool.get(key)
         if e is None or e["cap"] < n:
             e = pool[key] = {"hi": _keep_zeros(n, torch.int16, device), "lo": _keep_zeros(n, torch.int16, device),
@@ -921,15 +892,15 @@ class SatOps:
         if not _caches.trackable(t):          # inference tensor: no version counter, the emission cannot be validated later
             self._disc_emitted = None
             return
-        self._disc_emitted = {"ptr": t.data_ptr(), "ver": _caches.version_of(t), "key": key, "gen": self.__dict__.get("_disc_gen", {}).get(key, 0),
+        self._disc_emitted = {"ptr": t.data_ptr(), "ver": _caches.version_of(t), "key": key, "gen": self._disc_gen.get(key, 0),
                               "geom": (t.shape[0], (c + 7) // 8, frames, w), "planes": planes, "slot": slot}
 
     def disc_take(self, h, c, frames, w):
         """((hi, lo) planes of the pitched tensor h, their slot): the producer's emission if it is still intact, else a planes pass."""
-        e = self.__dict__.get("_disc_emitted")
+        e = self._disc_emitted
         self._disc_emitted = None
         if (e is not None and e["ptr"] == h.data_ptr() and _caches.trackable(h) and e["ver"] == _caches.version_of(h) and e["geom"] == (h.shape[0], (c + 7) // 8, frames, w)
-                and self.__dict__.get("_disc_gen", {}).get(e["key"], 0) == e["gen"]):
+                and self._disc_gen.get(e["key"], 0) == e["gen"]):
             return e["planes"], e["slot"]
         return self.disc_planes(h, frames, w, slot=0)[1], 0
 
@@ -1357,7 +1328,7 @@ class SatOps:
     gemm_tile = None     # None: pick per shape (_pick_tile); 0 = 128x128 (4 waves, 2 workgroups per CU), 4 = 256x256, 7 = 160x256, 8 = 128x128 (8 waves)
 
     def _zeros_page(self, device):
-        z = getattr(self, "_zpage", None)
+        z = self._zpage
         if z is None or z.device != device:
             z = _keep_zeros(64, torch.int16, device)
             self._zpage = z
@@ -1432,15 +1403,17 @@ class SatOps:
             c = self._reduce_rows(c.view(splits, m * nout), splits, m * nout).view(m, nout)
         return (c, pre) if want_pre and epilogue == self.EPI_SWIGLU else c
 
-    def _plane_cache(self, key, shape, device):
-        """Persistent zero-initialised bf16 planes for the no-grad path: rows / columns past the sequence length are never
-        written by the projection epilogue, so one memset at first use keeps them zero for every later call."""
-        cache = self.__dict__.setdefault("_planes", {})
-        t = cache.get(key)
-        if t is None or t.shape != shape or t.device != device:
-            t = _keep_zeros(shape, torch.int16, device)
-            cache[key] = t
-        return t
+    def _head_planes(self, nb, heads, ntok, sec0, nsec, reuse, device):
+        """The q / k / v_tr planes that sections sec0 .. sec0+nsec-1 of an attention input projection write: dict(n=, np=, q=, k=
+        (nb,H,Np,64), v_tr= (nb,H,64,Np)), zero-filled.  With `reuse` they are persistent (the no-grad path): rows / columns past the
+        sequence length are never written by the projection epilogue, so one memset at first use keeps them zero for every later call."""
+        npad = (ntok + 63) // 64 * 64
+        out = {"n": ntok, "np": npad}
+        for i, (name, shape) in enumerate((("q", (nb, heads, npad, 64)), ("k", (nb, heads, npad, 64)), ("v_tr", (nb, heads, 64, npad)))):
+            if sec0 <= i < sec0 + nsec:
+                out[name] = (self._workspace((reuse, name, shape), shape, torch.int16, device, zero=True) if reuse is not None
+                             else torch.zeros(shape, dtype=torch.int16, device=device))
+        return out
 
     def gemm_bf16_splitk(self, a, b, splits, bias=None, res=None, out_dtype=torch.bfloat16, out=None):
         """gemm_bf16 (epilogue: [+bias] [+res]) with K cut into `splits` ranges: fp32 slabs from the GEMM kernel, summed with the
@@ -1448,10 +1421,7 @@ class SatOps:
         m, n = a.shape[0], b.shape[0]
         st = self._stream(a)
         key = ("splitk", splits, m, n, a.device, st.value if st is not None else 0)      # one slab set per (device, stream)
-        slabs = self.__dict__.setdefault("_planes", {}).get(key)
-        if slabs is None:
-            slabs = _keep_empty((splits, m, n), torch.float32, a.device)
-            self._planes[key] = slabs
+        slabs = self._workspace(key, (splits, m, n), torch.float32, a.device)
         self._chk(self.lib.sat_gemm_bf16(_ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(slabs), n, None, None, 0, None, 0, 0, None, 0,
                                          _ptr(self._zeros_page(a.device)), m, n, a.shape[1], 0, 1, splits,
                                          self._pick_tile(m, n, splits, a.shape[1]), self._stream(a)))
@@ -1487,12 +1457,8 @@ class SatOps:
             raise TypeError("gemm_heads_bf16 takes bf16 operands")
         if x.stride(1) != 1 or w.stride(1) != 1 or w.shape[0] != nsec * heads * 64 or x.shape[0] != nb * ntok:
             raise ValueError("gemm_heads_bf16: bad operand layout")
-        npad = (ntok + 63) // 64 * 64
-        out = {"n": ntok, "np": npad}
-        for i, (name, shape) in enumerate((("q", (nb, heads, npad, 64)), ("k", (nb, heads, npad, 64)), ("v_tr", (nb, heads, 64, npad)))):
-            if sec0 <= i < sec0 + nsec:
-                out[name] = (self._plane_cache((reuse, name, shape), shape, x.device) if reuse is not None
-                             else torch.zeros(shape, dtype=torch.int16, device=x.device))
+        out = self._head_planes(nb, heads, ntok, sec0, nsec, reuse, x.device)
+        npad = out["np"]
         if cs is not None:
             self._f32(cs)
         if qk_norm is not None and qk_norm != "none":
@@ -1535,10 +1501,7 @@ class SatOps:
         # two launches: max|src| -> (448 / amax, amax / 448) on the device (sat_absmax_scale), then the conversion itself
         st = self._stream(src)
         wkey = ("absmax", src.device, st.value if st is not None else 0)
-        work = self.__dict__.setdefault("_planes", {}).get(wkey)
-        if work is None:
-            work = _keep_zeros(1 + 1024, torch.float32, src.device)
-            self._planes[wkey] = work
+        work = self._workspace(wkey, 1 + 1024, torch.float32, src.device, zero=True)
         scales = torch.empty(2, dtype=torch.float32, device=src.device)
         self._chk(self.lib.sat_absmax_scale(_ptr(src), src.stride(0), _ptr(work), _ptr(scales), src.shape[0], src.shape[1], int(dt == 0), st))
         q = torch.empty(src.shape, dtype=torch.uint8, device=src.device)
@@ -1601,12 +1564,8 @@ class SatOps:
 
     def gemm_heads_fp8(self, x, w, alpha, cs, heads, nb, ntok, sec0, nsec, reuse=None, row_alpha=None, col_alpha=None):
         """gemm_heads_bf16 on fp8 operands (planes come out in bf16); row_alpha / col_alpha as gemm_fp8."""
-        npad = (ntok + 63) // 64 * 64
-        out = {"n": ntok, "np": npad}
-        for i, (name, shape) in enumerate((("q", (nb, heads, npad, 64)), ("k", (nb, heads, npad, 64)), ("v_tr", (nb, heads, 64, npad)))):
-            if sec0 <= i < sec0 + nsec:
-                out[name] = (self._plane_cache((reuse, name, shape), shape, x.device) if reuse is not None
-                             else torch.zeros(shape, dtype=torch.int16, device=x.device))
+        out = self._head_planes(nb, heads, ntok, sec0, nsec, reuse, x.device)
+        npad = out["np"]
         alpha, col_alpha = self._fp8_alphas(alpha, col_alpha, w.shape[0])
         self._chk(self.lib.sat_gemm_qkv_fp8(_ptr(x), x.stride(0), _ptr(w), w.stride(0), _ptr(cs), (cs.shape[0] - ntok) if cs is not None else 0,
                                             _ptr(out.get("q")), _ptr(out.get("k")), _ptr(out.get("v_tr")), _ptr(self._zeros_page(x.device)),
