@@ -47,3 +47,13 @@ SAT_DEVICE SatSnakeGrad sat_snake_grad(float x, float a, float b) {
     g.dlb = -sq * ib * ib * b;
     return g;
 }
+// the same from s2 = sin(2 a x), c2 = cos(2 a x), the pair of sat_sincos2(a * x): for a kernel that evaluated it for sat_snake_sc already
+SAT_DEVICE SatSnakeGrad sat_snake_grad_sc(float x, float a, float b, float s2, float c2) {
+    const float ib = 1.0f / (b + 1e-9f);
+    const float sq = fmaf(-0.5f, c2, 0.5f);       // sin^2(a x)
+    SatSnakeGrad g;
+    g.dx = 1.0f + a * ib * s2;
+    g.dla = x * a * ib * s2;
+    g.dlb = -sq * ib * ib * b;
+    return g;
+}

@@ -23,10 +23,15 @@ int sat_check_launch(const char* what) {
     return 0;
 }
 extern "C" const char* sat_last_error() { return g_sat_err; }
-// compute units of the current device, queried once per thread (persistent kernels launch one workgroup per CU); 256 on the simulator
+// compute units of the current device, queried once per thread (persistent kernels launch one workgroup per CU); 256 on the simulator,
+// where a test may set another count to give a workgroup several tiles at a small shape (0 restores the default)
+#if defined(SAT_HIPEMU)
+static int g_sat_emu_cus = 256;
+extern "C" void sat_emu_set_cu_count(int n) { g_sat_emu_cus = n > 0 ? n : 256; }
+#endif
 int sat_cu_count() {
 #if defined(SAT_HIPEMU)
-    return 256;
+    return g_sat_emu_cus;
 #else
     static thread_local int dev_cached = -1, cus = 0;
     int dev = 0;

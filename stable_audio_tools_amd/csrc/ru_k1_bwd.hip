@@ -13,16 +13,19 @@
 // levels (3.5 - 3.8 TB/s; profiles/r04_vae_train_kernel_stats.csv: 23 ms of the 148-ms generator step).  Here one workgroup walks a
 // contiguous range of 32-step time tiles with ALL of the unit's dy channels and 128 of its h channels:
 //   * the tile of dy is converted once (bf16 hi / lo split, three MFMAs per product: fp32-class accuracy as everywhere on this path) into
-//     a natural [co][t] image (A operand of the weight gradient: 8 consecutive t per lane) AND a transposed [t][co] image (B operand of
-//     the data gradient: 8 consecutive co per lane); the tile of h becomes snake2(h) planes [ci][t] (B operand of the weight gradient);
+//     a natural [co][t] image: the A operand of the weight gradient (8 consecutive t per lane) as it lies, the B operand of the data
+//     gradient (8 consecutive co per lane) through transposing LDS reads; the tile of h becomes snake2(h) planes [ci][t] (B operand of
+//     the weight gradient);
 //   * data gradient (K = C over co) and weight gradient (K = 32 steps, accumulated in registers over the workgroup's whole range) run
 //     on v_mfma_f32_32x32x16_bf16; W2^T fragments come from L2 (a [ci][co] plane pair prepared once per step by sat_ru_k1_pack);
-//   * the epilogue runs in the STAGING layout (a thread owns four consecutive steps of a channel, its h values still in registers):
-//     dsnake2, the three per-channel sums (kept in registers across tiles: a thread's channels never change), 16-byte stores of dh, and
-//     — through a transposed LDS image — dh's activation planes for the k7 data-gradient that consumes it next (conv1d_planes.h layout).
-// Work per tile (C = 128): 65.5 KB of HBM traffic, 48 MFMAs per wave; two workgroups per CU (58 KB of LDS each).  Served: C = 128 (the
-// two widest levels of encoder and decoder: 12 of the 30 units, 78 % of the stack's activation bytes); other widths keep the separate
-// kernels (at C = 256 a wave's W2^T fragments no longer fit the register file beside its 128 accumulator registers).
+//   * the epilogue runs in the STAGING layout (a thread owns four consecutive steps of a channel, its h values and their sin / cos still
+//     in registers): dsnake2, the three per-channel sums (kept in registers across tiles: a thread's channels never change), 16-byte
+//     stores of dh, and — read back transposed from a wave-private bf16 image — dh's activation planes for the k7 data-gradient that
+//     consumes it next (conv1d_planes.h layout).
+// Work per tile (C = 128): 32 KB read, 16 KB of planes and (unless the caller wants the planes only) 16 KB of fp32 dh written: 12 or 16
+// bytes per element; 48 MFMAs per SIMD; one eight-wave workgroup per CU (142 KB of LDS: 78 KB of images, a 64-KB two-slot raw ring).
+// Served: C = 128 (the two widest levels of encoder and decoder: 12 of the 30 units, 78 % of the stack's activation bytes); other widths
+// keep the separate kernels (at C = 256 a wave's W2^T fragments no longer fit the register file beside its 128 accumulator registers).
 #include "conv_common.h"
 
 typedef uint32_t sat_u32x2 __attribute__((ext_vector_type(2)));
@@ -69,34 +72,58 @@ struct SatRuK1BwdParams {
     int B, C, T, em_rows, nsplit, tiles_per_split, ntiles;
 };
 
-// Eight waves, ONE workgroup per CU.  Staging, epilogue and emission are shared by all 512 threads (a thread owns four consecutive steps
+// counted wait with a run-time (wave-uniform) count: s_waitcnt takes an immediate.  Rounding DOWN to a served count only waits longer.
+#define SAT_RK_WAIT_VM(n)                                   \
+    do {                                                    \
+        if ((n) >= 8) { SAT_WAIT_VMCNT(8); }                \
+        else if ((n) >= 6) { SAT_WAIT_VMCNT(6); }           \
+        else if ((n) >= 4) { SAT_WAIT_VMCNT(4); }           \
+        else if ((n) >= 2) { SAT_WAIT_VMCNT(2); }           \
+        else { SAT_WAIT_VMCNT(0); }                         \
+    } while (0)
+
+// Eight waves, ONE workgroup per CU.  Conversion, epilogue and emission are shared by all 512 threads (a thread owns four consecutive steps
 // of channels (tid >> 3) and (tid >> 3) + 64); the matrix work is split by ROLE: waves 0-3 run the data gradient (wave w: ci rows
 // 32 w .. + 32 of the tile, K = 128 over co; its W2^T fragments — 32 rows x 128 co, hi + lo = 64 registers — stay resident: fetched per
 // k-step from L2 they serialised the loop behind sixteen dependent round trips per tile, the first timing of this kernel), waves 4-7
 // the weight gradient (a 64 x 64 block of dW2 each, accumulated over the workgroup's whole range: 64 registers).  Waves w and w + 4
 // share a SIMD, so every SIMD carries one wave of each role: 24 MFMAs per wave and tile on both.
+//
+// The tile loop is a two-phase software pipeline with TWO workgroup barriers per tile:
+//   V(i): epilogue of tile i - 1 (etile -> dsnake2, sums, dh, planes), then conversion of tile i (raw slot -> dyN, aN)      | barrier B
+//   M(i): the LDS-DMA of tile i + 2 goes out; the MFMAs of tile i; data-gradient waves leave W2^T dy in etile; wait DMA i+1 | barrier A
+// Every image has one writer phase and one reader phase with a barrier between them in both directions:
+//   raw slot (i & 1): DMA issued in M(i - 2) [its last reader V(i - 2) is a barrier B back], waited before A(i - 1), read in V(i);
+//   dyN / aN: written in V(i), read in M(i);     etile: written in M(i), read in V(i + 1).
+// Only the natural [channel][t] images exist: the [t][co] operand of the data gradient and the channel-minor rows of the plane emission
+// are TRANSPOSING reads of them (sat_lds_read_tr16_b64), not transposed 2-byte stores — those were 64 ds_write_b16 and ~48 shift / mask
+// VALU per thread and tile.  The emission is wave-local: a wave's epilogue rows are channels 8 w .. + 7 and 64 + 8 w .. + 7, two whole
+// 8-channel plane groups, so it writes its bf16 dh rows to a private 2.5-KB image and reads them back transposed with no workgroup barrier.
+// sin 2ah and cos 2ah of a tile's h are evaluated once, in the conversion, and kept (16 registers) for the epilogue one phase later.
 // The tiles of dy and h travel global -> LDS by LDS-DMA (32 one-KiB pieces per tile, four per wave) into a two-slot ring of raw fp32
-// images, one whole tile ahead, behind COUNTED waits and bare barriers: gfx950's vmcnt is one in-order counter for loads and stores, so
-// a register prefetch issued a tile ahead is waited for together with the stores between (measured: that version ran at 3.3 TB/s).
+// images behind COUNTED waits and bare barriers: gfx950's vmcnt is one in-order counter for loads and stores, so the wait for tile i + 1
+// counts the younger operations — the epilogue's stores of V(i) and the pieces of tile i + 2 — and leaves them in flight: no store is
+// ever waited for inside the loop (the first version waited vmcnt(4) right behind the epilogue's stores, every tile).
 template <int C>
 __global__ void __launch_bounds__(512) sat_ru_k1_bwd_kernel(SatRuK1BwdParams p) {
     static_assert(C == 128, "one 128-channel tile of h per workgroup, W2^T fragments in registers");
-    constexpr int TT = SAT_RK_TT, ROWN = SAT_RK_ROWN, ROWT = C + 8, EROW = SAT_RK_EROW;
+    constexpr int TT = SAT_RK_TT, ROWN = SAT_RK_ROWN, EROW = SAT_RK_EROW;
     constexpr int NJ = C / 64;                   // float4 slots of a (C x 32) tile per thread (C rows x 8 slots / 512 threads)
-    constexpr int DYT = 2 * TT * ROWT;           // shorts: transposed dy image, hi + lo   (also the transposed dh image of the emission)
-    constexpr int DYN = 2 * C * ROWN;            // natural dy image
-    constexpr int AN = 2 * C * ROWN;             // natural snake2(h) image   (also the fp32 epilogue tile)
+    constexpr int DYN = 2 * C * ROWN;            // shorts: natural dy image, hi + lo
+    constexpr int AN = 2 * C * ROWN;             // natural snake2(h) image
+    constexpr int ET = C * EROW;                 // floats: the epilogue tile
+    constexpr int WP = 2 * 8 * NJ * ROWN;        // shorts: one wave's dh rows (hi + lo planes of 8 NJ channels) for the emission
     constexpr int RAW = 2 * C * TT;              // floats: one raw tile = dy rows 0 .. C-1, h rows C .. 2C-1, 32 steps (128 B) each
-    static_assert(C * EROW * 4 <= AN * 2, "the epilogue tile aliases the snake2(h) image");
     static_assert(TT * 4 == 128, "a raw row is eight 16-byte DMA lanes");
+    static_assert(NJ == 2, "the emission maps a wave's 64 lanes to 2 plane groups x 32 steps");
+    static_assert((DYN + AN + 8 * WP) * 2 + ET * 4 + 2 * RAW * 4 <= 160 * 1024, "LDS of one CU");
     // ONE shared object (a second one makes hipcc drain the DMA queue before every LDS read: cdna_hip_programming.md section 5)
-    __shared__ __attribute__((aligned(16))) char smem[(DYT + DYN + AN) * 2 + 2 * RAW * 4];
-    short* dyT = reinterpret_cast<short*>(smem);  // [plane][t][ROWT]
-    short* dyN = dyT + DYT;                      // [plane][co][ROWN]
+    __shared__ __attribute__((aligned(16))) char smem[(DYN + AN + 8 * WP) * 2 + ET * 4 + 2 * RAW * 4];
+    short* dyN = reinterpret_cast<short*>(smem); // [plane][co][ROWN]
     short* aN = dyN + DYN;                       // [plane][ci][ROWN]
-    float* etile = reinterpret_cast<float*>(aN); // [ci][EROW]
-    short* dhT = dyT;                            // [plane][t][ROWT]: dh transposed, for the emission
-    float* raw = reinterpret_cast<float*>(smem + (DYT + DYN + AN) * 2);      // [slot][2C][32]
+    float* etile = reinterpret_cast<float*>(aN + AN);                        // [ci][EROW]
+    short* wpriv = reinterpret_cast<short*>(etile + ET);                     // [wave][plane][8 j + row][ROWN]
+    float* raw = reinterpret_cast<float*>(wpriv + 8 * WP);                   // [slot][2C][32]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = SAT_UNIFORM((int)(threadIdx.x >> 6));
@@ -111,12 +138,11 @@ __global__ void __launch_bounds__(512) sat_ru_k1_bwd_kernel(SatRuK1BwdParams p) 
 
     // this thread's slots of a tile: channels (tid >> 3) + 64 j, steps 4 (tid & 7) .. + 3
     const int srow = tid >> 3, st4 = (tid & 7) * 4;
-    // Transposed images [t][channel]: the 16-byte channel groups of row t are stored at group ^ ((t >> 3) & 3).  A wave's 2-byte
-    // transposed stores go to rows 0, 4, .. 28 of the same channel: at a row stride of 272 bytes those are two banks without the
-    // swizzle (4-way conflicts on every one of the 32 stores per thread and tile — the first versions of this kernel spent a third of
-    // their time there) and eight with it; the 16-byte reads (fragments, plane emission) apply the same XOR.
-    const int swz_w = ((st4 >> 3) & 3) << 3;      // writer: rows st4 .. st4 + 3 share (t >> 3)
-    const int swz_f = ((l31 >> 3) & 3) << 3;      // fragment reader: row l31
+    // Transposing reads (sat_lds_read_tr16_b64): the 16-lane group (lane >> 4) reads a block of 4 rows x 16 steps; lane 4 q + pp of the
+    // group supplies row q, steps 4 pp .. + 3 and receives step (lane & 15) of the four rows.  Groups 0 / 1 take steps 0-15 / 16-31, so a
+    // lane receives step l31; groups 2 / 3 repeat that 8 rows further down (hi).  Two reads, 4 rows apart, make 8 consecutive channels at
+    // one step: the MFMA B fragment of the data gradient (k = co), or the 16 bytes of a plane row.
+    const int tr_off = (8 * hi + ((lane >> 2) & 3)) * ROWN + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);      // shorts
     float sa[NJ], sb[NJ], sib[NJ];               // snake2 constants of the thread's h channels
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -125,6 +151,10 @@ __global__ void __launch_bounds__(512) sat_ru_k1_bwd_kernel(SatRuK1BwdParams p) 
         sb[j] = expf(p.beta2[ci]);
         sib[j] = 1.0f / (sb[j] + 1e-9f);
     }
+#if !defined(SAT_HIPEMU)
+    // (computed here, not where first used: hipcc's own wait for these loads does not count the LDS-DMA pieces issued in between)
+    asm volatile("" : "+v"(sa[0]), "+v"(sa[1]), "+v"(sb[0]), "+v"(sb[1]), "+v"(sib[0]), "+v"(sib[1]));
+#endif
     float sum_da[NJ], sum_db[NJ], sum_dh[NJ], sum_dy[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) sum_da[j] = sum_db[j] = sum_dh[j] = sum_dy[j] = 0.0f;
@@ -166,21 +196,64 @@ __global__ void __launch_bounds__(512) sat_ru_k1_bwd_kernel(SatRuK1BwdParams p) 
         for (int q = 0; q < 4; ++q) {
             const int piece = wave + 8 * q;                       // rows 8 piece ..: channels 8 (piece & 15) .. of dy (q < 2) or h
             const float* src = (q < 2 ? p.dy : p.h) + base + (size_t)(8 * (piece & 15)) * p.T;
-            sat_glds16(src, slot + piece * 1024);
+            sat_glds16_raw(src, slot + piece * 1024);           // (opaque to hipcc: behind the builtin it drains the queue before every transposing read)
         }
     };
-    if (tile_begin < tile_end) dma_tile(tile_begin);
+    // global stores of one epilogue per wave (block-uniform): they are younger than the DMA the next wait is for
+    const int nst = (p.dh ? NJ : 0) + (p.em_hi ? 2 : 0);
+    if (tile_begin < tile_end) {
+        dma_tile(tile_begin);
+        if (tile_begin + 1 < tile_end) { dma_tile(tile_begin + 1); SAT_WAIT_VMCNT(4); } else { SAT_WAIT_VMCNT(0); }
+    }
+    SAT_RAW_BARRIER();
 
-    for (int tile = tile_begin; tile < tile_end; ++tile) {
-        const int b = tile / tiles_per_b, t0 = (tile - b * tiles_per_b) * TT;
+    f32x4 hv[NJ], s2v[NJ], c2v[NJ];              // the tile's h and sin / cos (2 a h): conversion -> epilogue, one phase later
+    int pb = 0, pt0 = 0;                         // batch item and first step of the tile whose epilogue is due
+    for (int tile = tile_begin; tile <= tile_end; ++tile) {
+        // ---- V, first half: epilogue of tile - 1: dsnake2, the per-channel sums, dh (16-byte stores), dh's planes ----
+        if (tile > tile_begin) {
+            short* wp = wpriv + wave * WP;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int ch = srow + 64 * j;
+                const f32x4 pre = *reinterpret_cast<const f32x4*>(etile + ch * EROW + st4);
+                f32x4 out;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const SatSnakeGrad g = sat_snake_grad_sc(hv[j][e], sa[j], sb[j], s2v[j][e], c2v[j][e]);
+                    sum_da[j] += pre[e] * g.dla;
+                    sum_db[j] += pre[e] * g.dlb;
+                    out[e] = pre[e] * g.dx;
+                    sum_dh[j] += out[e];
+                }
+                if (p.dh) *reinterpret_cast<f32x4*>(p.dh + ((size_t)pb * C + ch) * p.T + pt0 + st4) = out;      // (block-uniform; null: only the planes are wanted)
+                if (p.em_hi) {
+                    uint32_t h0, l0, h1, l1;
+                    sat_split2_pk(out[0], out[1], &h0, &l0);
+                    sat_split2_pk(out[2], out[3], &h1, &l1);
+                    short* wr = wp + (8 * j + (lane >> 3)) * ROWN + st4;
+                    *reinterpret_cast<sat_u32x2*>(wr) = sat_u32x2{h0, h1};
+                    *reinterpret_cast<sat_u32x2*>(wr + 8 * NJ * ROWN) = sat_u32x2{l0, l1};
+                }
+            }
+            // plane emission: lane = (plane group j = hi, step l31): a row of 8 channels at one step, 16 bytes (consecutive lanes =
+            // consecutive steps).  The image is this wave's own: its LDS operations execute in order, no barrier
+            if (p.em_hi) {
+                SAT_WAIT_LGKM0();
+                sat_wave_sync();
+                const bf16x4 h0 = sat_lds_read_tr16_b64(wp + tr_off), h1 = sat_lds_read_tr16_b64(wp + tr_off + 4 * ROWN);
+                const bf16x4 l0 = sat_lds_read_tr16_b64(wp + 8 * NJ * ROWN + tr_off), l1 = sat_lds_read_tr16_b64(wp + 8 * NJ * ROWN + tr_off + 4 * ROWN);
+                const size_t o = (((size_t)pb * (C / 8) + wave + 8 * hi) * p.em_rows + SAT_RK_LEAD + pt0 + l31) * 8;
+                *reinterpret_cast<bf16x8*>(p.em_hi + o) = bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+                *reinterpret_cast<bf16x8*>(p.em_lo + o) = bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+                sat_wave_sync();                  // (the simulator's lanes: all have read before the next epilogue writes)
+            }
+        }
+        if (tile == tile_end) break;
+        pb = tile / tiles_per_b;
+        pt0 = (tile - pb * tiles_per_b) * TT;
+        // ---- V, second half: conversion of this tile: split dy, snake2(h) (natural images) ----
         const float* rt = raw + (tile & 1) * RAW;
-        // the next tile's pieces go out first (their slot was last read in the previous tile's epilogue, a barrier ago); then this wave's
-        // pieces of THIS tile are waited for: everything it issued since — the previous tile's stores and the four new pieces — is younger
-        const bool more = tile + 1 < tile_end;
-        if (more) { dma_tile(tile + 1); SAT_WAIT_VMCNT(4); } else { SAT_WAIT_VMCNT(0); }
-        SAT_RAW_BARRIER();
-        // ---- P1: split dy (natural + transposed images), snake2(h) (natural image) ----
-        f32x4 hv[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int ch = srow + 64 * j;
@@ -191,46 +264,45 @@ __global__ void __launch_bounds__(512) sat_ru_k1_bwd_kernel(SatRuK1BwdParams p) 
             sat_split2_pk(dyv[2], dyv[3], &h1, &l1);
             *reinterpret_cast<sat_u32x2*>(dyN + ch * ROWN + st4) = sat_u32x2{h0, h1};
             *reinterpret_cast<sat_u32x2*>(dyN + C * ROWN + ch * ROWN + st4) = sat_u32x2{l0, l1};
-            const int cs = ch ^ swz_w;
-            dyT[(st4 + 0) * ROWT + cs] = (short)(h0 & 0xffffu);
-            dyT[(st4 + 1) * ROWT + cs] = (short)(h0 >> 16);
-            dyT[(st4 + 2) * ROWT + cs] = (short)(h1 & 0xffffu);
-            dyT[(st4 + 3) * ROWT + cs] = (short)(h1 >> 16);
-            dyT[TT * ROWT + (st4 + 0) * ROWT + cs] = (short)(l0 & 0xffffu);
-            dyT[TT * ROWT + (st4 + 1) * ROWT + cs] = (short)(l0 >> 16);
-            dyT[TT * ROWT + (st4 + 2) * ROWT + cs] = (short)(l1 & 0xffffu);
-            dyT[TT * ROWT + (st4 + 3) * ROWT + cs] = (short)(l1 >> 16);
             sum_dy[j] += (dyv[0] + dyv[1]) + (dyv[2] + dyv[3]);
             float v[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = sat_snake(hv[j][e], sa[j], sib[j]);
+            for (int e = 0; e < 4; ++e) {
+                float s2, c2;
+                sat_sincos2(hv[j][e] * sa[j], &s2, &c2);
+                s2v[j][e] = s2;
+                c2v[j][e] = c2;
+                v[e] = sat_snake_sc(hv[j][e], sib[j], c2);
+            }
             sat_split2_pk(v[0], v[1], &h0, &l0);
             sat_split2_pk(v[2], v[3], &h1, &l1);
             *reinterpret_cast<sat_u32x2*>(aN + ch * ROWN + st4) = sat_u32x2{h0, h1};
             *reinterpret_cast<sat_u32x2*>(aN + C * ROWN + ch * ROWN + st4) = sat_u32x2{l0, l1};
         }
         SAT_WAIT_LGKM0();
-        SAT_RAW_BARRIER();
+        SAT_RAW_BARRIER();                        // B: the images of this tile are complete; its raw slot is free
 
-        // ---- P2: the matrix work, by role ----
+        // ---- M: the matrix work, by role; the pieces of tile + 2 go out first, into the slot this tile's conversion just left ----
+        const bool ahead = tile + 2 < tile_end;
+        if (ahead) dma_tile(tile + 2);
         if (dgrad_wave) {
             f32x16 accd;
 #pragma unroll
             for (int r = 0; r < 16; ++r) accd[r] = 0.0f;
-            const short* brow = dyT + l31 * ROWT;
+            const short* brow = dyN + tr_off;
 #pragma unroll
             for (int s = 0; s < C / 16; ++s) {
-                const int col = (16 * s + 8 * hi) ^ swz_f;
-                const bf16x8 bh = *reinterpret_cast<const bf16x8*>(brow + col);
-                const bf16x8 bl = *reinterpret_cast<const bf16x8*>(brow + TT * ROWT + col);
+                const short* bs = brow + 16 * s * ROWN;
+                const bf16x4 bh0 = sat_lds_read_tr16_b64(bs), bh1 = sat_lds_read_tr16_b64(bs + 4 * ROWN);
+                const bf16x4 bl0 = sat_lds_read_tr16_b64(bs + C * ROWN), bl1 = sat_lds_read_tr16_b64(bs + C * ROWN + 4 * ROWN);
+                const bf16x8 bh = {bh0[0], bh0[1], bh0[2], bh0[3], bh1[0], bh1[1], bh1[2], bh1[3]};
+                const bf16x8 bl = {bl0[0], bl0[1], bl0[2], bl0[3], bl1[0], bl1[1], bl1[2], bl1[3]};
                 const bf16x8 wh = sat_rk_frag(big[s >> 2], s & 3), wl = sat_rk_frag(big[2 + (s >> 2)], s & 3);
                 accd = sat_mfma_32x32x16_bf16(wh, bh, accd);
                 accd = sat_mfma_32x32x16_bf16(wh, bl, accd);
                 accd = sat_mfma_32x32x16_bf16(wl, bh, accd);
             }
-            SAT_WAIT_LGKM0();
-            SAT_RAW_BARRIER();                    // every fragment read of the tile is done (both roles): the images may be overwritten
-            // ---- P3: W2^T dy from the accumulator layout into the epilogue tile [ci][t] ----
+            // W2^T dy from the accumulator layout into the epilogue tile [ci][t] (its last readers are two barriers back)
 #pragma unroll
             for (int r = 0; r < 16; ++r) etile[(32 * wq + (r & 3) + 8 * (r >> 2) + 4 * hi) * EROW + l31] = accd[r];
         } else {
@@ -256,55 +328,13 @@ __global__ void __launch_bounds__(512) sat_ru_k1_bwd_kernel(SatRuK1BwdParams p) 
                     }
                 }
             }
-            SAT_WAIT_LGKM0();
-            SAT_RAW_BARRIER();                    // (pairs with the data-gradient waves' barrier)
         }
+        // this wave's pieces of tile + 1 have landed: younger than them are the stores of this tile's V phase (the epilogue of tile - 1)
+        // and the pieces of tile + 2
+        const int younger = (ahead ? 4 : 0) + (tile > tile_begin ? nst : 0);
+        SAT_RK_WAIT_VM(younger);
         SAT_WAIT_LGKM0();
-        SAT_RAW_BARRIER();
-
-        // ---- P4: dsnake2, the per-channel sums, dh (16-byte stores) and its transposed bf16 image ----
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int ch = srow + 64 * j;
-            const f32x4 pre = *reinterpret_cast<const f32x4*>(etile + ch * EROW + st4);
-            f32x4 out;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const SatSnakeGrad g = sat_snake_grad(hv[j][e], sa[j], sb[j]);
-                sum_da[j] += pre[e] * g.dla;
-                sum_db[j] += pre[e] * g.dlb;
-                out[e] = pre[e] * g.dx;
-                sum_dh[j] += out[e];
-            }
-            if (p.dh) *reinterpret_cast<f32x4*>(p.dh + ((size_t)b * C + ch) * p.T + t0 + st4) = out;      // (block-uniform; null: only the planes are wanted)
-            if (p.em_hi) {
-                uint32_t h0, l0, h1, l1;
-                sat_split2_pk(out[0], out[1], &h0, &l0);
-                sat_split2_pk(out[2], out[3], &h1, &l1);
-                const int cs = ch ^ swz_w;
-                dhT[(st4 + 0) * ROWT + cs] = (short)(h0 & 0xffffu);
-                dhT[(st4 + 1) * ROWT + cs] = (short)(h0 >> 16);
-                dhT[(st4 + 2) * ROWT + cs] = (short)(h1 & 0xffffu);
-                dhT[(st4 + 3) * ROWT + cs] = (short)(h1 >> 16);
-                dhT[TT * ROWT + (st4 + 0) * ROWT + cs] = (short)(l0 & 0xffffu);
-                dhT[TT * ROWT + (st4 + 1) * ROWT + cs] = (short)(l0 >> 16);
-                dhT[TT * ROWT + (st4 + 2) * ROWT + cs] = (short)(l1 & 0xffffu);
-                dhT[TT * ROWT + (st4 + 3) * ROWT + cs] = (short)(l1 >> 16);
-            }
-        }
-        SAT_WAIT_LGKM0();
-        SAT_RAW_BARRIER();
-
-        // ---- P5: plane emission: rows of 8 channels at one step, 16 bytes each (consecutive threads = consecutive steps) ----
-        if (p.em_hi) {
-            const int t = tid & 31, g = tid >> 5;                              // g: 8-channel group (0..15)
-            const size_t o = (((size_t)b * (C / 8) + g) * p.em_rows + SAT_RK_LEAD + t0 + t) * 8;
-            const int gs = (8 * g) ^ (((t >> 3) & 3) << 3);
-            *reinterpret_cast<u32x4*>(p.em_hi + o) = *reinterpret_cast<const u32x4*>(dhT + t * ROWT + gs);
-            *reinterpret_cast<u32x4*>(p.em_lo + o) = *reinterpret_cast<const u32x4*>(dhT + TT * ROWT + t * ROWT + gs);
-            SAT_WAIT_LGKM0();
-            SAT_RAW_BARRIER();                    // the transposed image aliases the next tile's transposed dy image
-        }
+        SAT_RAW_BARRIER();                        // A: every fragment read of the tile is done, etile is complete, tile + 1 is in its slot
     }
 
     // ---- the workgroup's dW2 slab and its per-channel sums ----

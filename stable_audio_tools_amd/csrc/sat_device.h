@@ -306,6 +306,10 @@ SAT_DEVICE float sat_sin2(float y) {
 SAT_DEVICE float sat_snake(float x, float a, float ib) {
     return fmaf(ib, sat_sin2(x * a), x);
 }
+// the same from c2 = cos(2 a x) of sat_sincos2(x * a): for a kernel that keeps the pair for sat_snake_grad_sc (conv_common.h)
+SAT_DEVICE float sat_snake_sc(float x, float ib, float c2) {
+    return fmaf(ib, fmaf(-0.5f, c2, 0.5f), x);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Launch + status plumbing shared by every C-ABI entry point.
