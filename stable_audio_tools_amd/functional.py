@@ -98,10 +98,10 @@ class WeightNormFn(torch.autograd.Function):
 
 def _conv_dgrad(ops, dy, w, k, stride, dil, pad, cin, tin, dsnake, res=None, out=None, emit=None):
     """dL/d(conv input pre-activation) of a Conv1d with torch weight w (Cout, Cin, K).  out= (stride-1 kernels only): write into
-    the caller's tensor (it may alias `res`: accumulation in place).  emit: {"snake": None | (la, lb)} — also write the result as
-    the activation planes of the k7 conv that consumes it next (ops.emit_ok decides)."""
+    the caller's tensor (it may alias `res`: accumulation in place).  emit (ops.conv1d_bf16x3): True — also write the result as the
+    activation planes of the k7 conv that consumes it next (ops.emit_ok decides)."""
     if stride == 1:
-        if (res is None and out is None and emit is None and ops.edge_ok(w.shape[0], cin, k, 1, dil, (k - 1) * dil - pad) and tin == dy.shape[2]
+        if (res is None and out is None and not emit and ops.edge_ok(w.shape[0], cin, k, 1, dil, (k - 1) * dil - pad) and tin == dy.shape[2]
                 and (dsnake is None or w.shape[0] <= 2)):
             # the data-gradient of a conv with a two-channel side = that side's edge conv on the transposed, tap-flipped weight
             return ops.edge_conv(dy, w, (k - 1) * dil - pad, mode=1, dsnake=dsnake)
@@ -152,24 +152,26 @@ def _wn_backward(ops, slabs, saved, g_shape, bias_partial=None):
 
 
 def _conv_fwd(ops, x, w, stride, dil, pad, bias=None, snake=None, res=None, tanh_out=False, dsnake=None, tout=None, cache=None, emit=None,
-              keep_planes=None):
+              keep_planes=False):
     """conv1d(snake(x), w) [+bias] [+res]: the bf16x3 split-MFMA kernel (fp32-accurate, csrc/conv1d_bf16x3.hip) where
     its shape rules allow, else the fp32-MFMA kernel (csrc/conv1d.hip).  cache: DerivedCache of the layer (no-grad / frozen
-    passes only) for the packed planes and the SnakeBeta constants.  keep_planes: a dict — a plane-fed k7 conv then reads its planes
-    from the buffer it owns and leaves their handle in keep_planes["kept"] (ops.conv1d_bf16x3); other convs leave it untouched."""
+    passes only) for the packed planes and the SnakeBeta constants.  emit, keep_planes: as ops.conv1d_bf16x3 — keep_planes=True returns
+    (y, kept), `kept` the handle of the planes a plane-fed k7 conv read from the buffer it owns, None for every other conv."""
     cout, cin, k = w.shape
     if (res is None and ops.edge_ok(cin, cout, k, stride, dil, pad) and (tout is None or tout == x.shape[2])
-            and (snake is None or cout <= 2) and (dsnake is None or cin <= 2) and (emit is None or cin <= 2)):
+            and (snake is None or cout <= 2) and (dsnake is None or cin <= 2) and (not emit or cin <= 2)):
         # a two-channel end of the stack (the encoder's first conv, the decoder's last): fp32 FMA stream straight from the folded weight
-        return ops.edge_conv(x, w, pad, bias=bias, snake=snake, tanh_out=tanh_out, dsnake=dsnake, emit=emit)
-    if ops.bf16x3_ok(k, stride, dil):
+        y = ops.edge_conv(x, w, pad, bias=bias, snake=snake, tanh_out=tanh_out, dsnake=dsnake, emit=emit)
+    elif ops.bf16x3_ok(k, stride, dil):
         q = ops.k7q_applicable(cin, k, stride, dil, pad, cout)
         planes = _cached(cache, "pack_fwd_q" if q else "pack_fwd", (w,), lambda: ops.pack_bf16x3(w, stride=stride, q=q))
         sconsts = _cached(cache, "snake", snake, lambda: ops.snake_consts(snake[0], snake[1])) if snake is not None else None
         return ops.conv1d_bf16x3(x, planes, cout, k, stride, dil, pad, tout=tout, bias=bias,
                                  snake=snake, res=res, tanh_out=tanh_out, dsnake=dsnake, sconsts=sconsts, emit=emit, keep_planes=keep_planes)
-    return ops.conv1d(x, _cached(cache, "pack_fwd32", (w,), lambda: ops.pack(w, PACK_CONV_FWD)), cout, k, stride, dil, pad, tout=tout,
-                      bias=bias, snake=snake, res=res, tanh_out=tanh_out, dsnake=dsnake)
+    else:
+        y = ops.conv1d(x, _cached(cache, "pack_fwd32", (w,), lambda: ops.pack(w, PACK_CONV_FWD)), cout, k, stride, dil, pad, tout=tout,
+                       bias=bias, snake=snake, res=res, tanh_out=tanh_out, dsnake=dsnake)
+    return (y, None) if keep_planes else y
 
 
 def _convtr_fwd(ops, x, w, stride, pad, bias=None, snake=None, cache=None):
@@ -204,7 +206,7 @@ class SnakeConv1dFn(torch.autograd.Function):
             tout_ = (x.shape[2] + 2 * pad - dil * (k - 1) - 1) // stride + 1
             if ((ops.emit_ok(cout, k, stride, tout_, next_snake[2]) and ops.bf16x3_ok(k, stride, dil))
                     or (res is None and snake is None and ops.edge_emit_ok(cin, cout, k, stride, dil, pad, next_snake[2]))):
-                emit = {"snake": (next_snake[0].detach(), next_snake[1].detach())}
+                emit = (next_snake[0].detach(), next_snake[1].detach())
         y = _conv_fwd(ops, x, w, stride, dil, pad, bias=bias, snake=snake,
                       res=res.contiguous() if res is not None else None, tanh_out=tanh_out, cache=cache, emit=emit)
         ctx.ops = ops
@@ -315,9 +317,9 @@ class ResidualUnitFn(torch.autograd.Function):
         k1 = w1.shape[2]
         pad = dil * (k1 - 1) // 2
         c1, c2 = caches if caches is not None else (None, None)
-        emit = None
+        emit = ctx.k7_planes = None
         if next_snake is not None and ops.emit_ok(c, w2.shape[2], 1, x.shape[2], next_snake[2]):
-            emit = {"snake": (next_snake[0].detach(), next_snake[1].detach())}
+            emit = (next_snake[0].detach(), next_snake[1].detach())
         if fuse and w2.shape[2] == 1 and w1.shape[0] == c and ops.ru_fused_ok(c, k1, dil, x.shape[2]):
             # C <= 128: the whole unit in ONE launch (csrc/conv1d_bf16x3_k7q.h, FUSED) — the k1 launch and its read of h disappear
             w7q = _cached(c1, "pack_q7", (w1,), lambda: ops.pack_k7q(w1))
@@ -329,10 +331,10 @@ class ResidualUnitFn(torch.autograd.Function):
                                          emit=emit, sconsts=sc)
         else:
             # a backward will follow: the planes the k7 conv reads stay in its own buffer for the weight gradient (ops.wgrad7_planes)
-            keep = {} if (ops.wgrad7_planes and not recompute and ctx is not None and any(ctx.needs_input_grad)) else None
+            keep = bool(ops.wgrad7_planes and not recompute and any(ctx.needs_input_grad))
             h = _conv_fwd(ops, x, w1, 1, dil, pad, bias=bias1, snake=(a1, b1), cache=c1, keep_planes=keep)
-            if ctx is not None:
-                ctx.k7_planes = keep.get("kept") if keep is not None else None
+            if keep:
+                h, ctx.k7_planes = h
             y = _conv_fwd(ops, h, w2, 1, 1, 0, bias=bias2, snake=(a2, b2), res=x, cache=c2, emit=emit)
         ctx.ops = ops
         ctx.dil = dil
@@ -359,27 +361,21 @@ class ResidualUnitFn(torch.autograd.Function):
             h = _conv_fwd(ops, x, w1, 1, dil, pad1, bias=bias1, snake=(a1, b1))
         # the k1 data-gradient also writes dh as the planes its consumer — the k7 data-gradient two launches below — reads
         want_emit = ops.emit_ok(w1.shape[0], k2, 1, t, dil) and ops.k7q_applicable(w1.shape[0], k1, 1, dil, pad1, c)
-        # the k7 weight gradient from planes (csrc/conv_wgrad7_planes.h): dh's, emitted below, and the ones the forward conv read — if they
-        # are still what it read (ops.kept_planes_valid); anything else keeps the fp32 kernel
-        kp = getattr(ctx, "k7_planes", None)
-        bsz = dy.shape[0]
+        # the k7 weight gradient from planes (csrc/conv_wgrad7_planes.h): dh's, emitted below, and the ones the forward conv kept — if they
+        # are still what it read; anything else keeps the fp32 kernel
+        kept = ctx.k7_planes if not ctx.recompute and want_emit and ops.kept_planes_valid(ctx.k7_planes, x, (a1, b1), dil, pad1) else None
         skip_dh = False
-        if kp is not None and not (not ctx.recompute and want_emit and k1 == 7 and w1.shape[0] == c
-                                   and ops.kept_planes_valid(kp, x, (a1, b1), dil, pad1)):
-            kp = None
 
         def wgrad1(dh, bias_grad):
-            em = ops._peek_emitted(dh, None) if kp is not None else None
-            if em is None or not ops.conv_wgrad7_planes_ok(bsz, c, c, t, dil, pad1, em["rows"], kp["buf"]["rows"]):
+            dw = ops.conv_wgrad7_from_planes(dh, kept, x, (a1, b1), dil, pad1, raw=bool(wn1))
+            if dw is None:
                 return _conv_wgrad(ops, dh, x, k1, 1, dil, pad1, (a1, b1), bias_grad=bias_grad, raw=bool(wn1))
-            dw = ops.conv_wgrad7_planes((em["hi"], em["lo"], em["rows"]), (kp["buf"]["hi"], kp["buf"]["lo"], kp["buf"]["rows"]),
-                                        bsz, c, c, t, dil, pad1, raw=bool(wn1))
             return (dw, ops.rowsum(dh, partial=bool(wn1))) if bias_grad else dw
         if k2 == 1 and w2.shape[0] == c and w1.shape[0] == c and ops.ru_k1_bwd_ok(dy.shape[0], c, t):
             # C == 128 (the widest levels): weight gradient, data gradient, both bias gradients and the snake gradients of the 1x1 conv in ONE pass
             # over dy and h (csrc/ru_k1_bwd.hip) instead of three kernels that each stream them from HBM
             # (both consumers of dh read its planes: the kernel then does not store fp32 dh at all)
-            skip_dh = bool(kp is not None and ops.ru_k1_bwd_skip_dh)
+            skip_dh = bool(kept is not None and ops.ru_k1_bwd_skip_dh)
             dh, da2, db2, dw2, dbias2, dbias1 = ops.ru_k1_bwd(dy, h, w2, (a2, b2), emit=want_emit, raw=bool(wn2), skip_dh=skip_dh)
             # (a skipped dh is marked in ops until this backward ends: every fp32 reader of it raises instead of reading garbage)
             try:
@@ -390,7 +386,7 @@ class ResidualUnitFn(torch.autograd.Function):
                 ops.dh_written()
         else:
             dw2, dbias2 = ops.conv_wgrad(dy, h, k2, 1, 1, 0, snake=(a2, b2), snake_on=2, lo_rowsum=True, raw=bool(wn2))
-            dh, da2, db2 = _conv_dgrad(ops, dy, w2, k2, 1, 1, 0, c, t, (h, a2, b2), emit={"snake": None} if want_emit else None)
+            dh, da2, db2 = _conv_dgrad(ops, dy, w2, k2, 1, 1, 0, c, t, (h, a2, b2), emit=want_emit)
             dw1, dbias1 = wgrad1(dh, True)
         dg1 = dg2 = None
         if wn1:         # a raw weight gradient brings its bias gradient as per-split sums (C, R): finished in the same launch

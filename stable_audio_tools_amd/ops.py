@@ -57,14 +57,53 @@ class WgradSlabs:
         raise ValueError("WgradSlabs.reduce: unknown slab layout %s" % (self.strides,))
 
 
+def _snake_key(snake):
+    return None if snake is None else (snake[0].data_ptr(), snake[1].data_ptr(), _caches.version_of(snake[0]), _caches.version_of(snake[1]))
+
+
+class Planes:
+    """bf16 hi / lo planes [B][ceil(C/8)][rows][8] of act(x) and what they hold (set by of()): x's storage, shape and version, and the
+    SnakeBeta parameters' storage and versions (None: act = identity).  own / gen: the OwnedPlanes they were written into and its write
+    count at that time (None: a shared buffer, valid only until the next producer).  The k7 section of SatOps says who makes them."""
+    __slots__ = ("hi", "lo", "rows", "own", "gen", "ptr", "shape", "ver", "snake")
+
+    def __init__(self, hi, lo, rows, own=None):
+        self.hi, self.lo, self.rows, self.own, self.gen = hi, lo, rows, own, own.gen if own is not None else None
+        self.ptr = self.shape = self.ver = self.snake = None
+
+    def __getitem__(self, name):        # planes["hi"] / ["lo"] / ["rows"], as the kernel tests read what _take_emitted returns
+        return getattr(self, name)
+
+    def of(self, x, snake):
+        self.ptr, self.shape, self.ver, self.snake = x.data_ptr(), tuple(x.shape), _caches.version_of(x), _snake_key(snake)
+        return self
+
+    def holds(self, x, snake):
+        """Are these still act(x) for this x and these parameters, in a buffer nobody rewrote?  (Inference tensors: never — no version.)"""
+        return (self.ptr == x.data_ptr() and self.shape == tuple(x.shape) and _caches.trackable(x) and self.ver == _caches.version_of(x)
+                and self.snake == _snake_key(snake) and (self.own is None or self.gen == self.own.gen))
+
+
+class OwnedPlanes:
+    """The plane buffer one k7 conv owns (SatOps._owned_planes): zero-filled once, used from `stream`, `gen` counts its rewrites."""
+    __slots__ = ("hi", "lo", "rows", "gen", "stream")
+
+    def __init__(self, n, rows, device, stream):
+        self.hi, self.lo, self.rows, self.gen, self.stream = _keep_zeros(n, torch.int16, device), _keep_zeros(n, torch.int16, device), rows, 0, stream
+
+    def rewrite(self):
+        self.gen += 1
+        return Planes(self.hi, self.lo, self.rows, self)
+
+
 class SatOps:
     def __init__(self, cdll):
         self.lib = cdll
         self.simulator = bool(cdll.sat_is_simulator())
         # every piece of mutable state of the object (release_workspaces / release_owned_planes empty it again)
         self._planes = {}           # _workspace: key -> cached tensor
-        self._own_planes = {}       # _owned_planes: the plane buffers the k7 convs own
-        self._emitted = None        # _note_emitted: the planes a producer wrote for the conv that reads its output next
+        self._own_planes = {}       # _owned_planes: key -> OwnedPlanes, the plane buffers the k7 convs own
+        self._emitted = None        # _emit_done: the Planes a producer wrote for the conv that reads its output next
         self._dh_unwritten = None   # ru_k1_bwd(skip_dh=True): address of the dh that exists only as planes
         self._zpage = None          # _zeros_page
         self._disc_pool, self._disc_gen, self._disc_geoms = {}, {}, {}      # _disc_plane_buf / disc_geom
@@ -214,7 +253,8 @@ class SatOps:
     def edge_conv(self, x, w, pad, mode=0, bias=None, snake=None, tanh_out=False, dsnake=None, emit=None):
         """conv1d(snake(x), W) + bias for a conv with <= 2 channels on one side (edge_ok).  w: the FOLDED torch weight — (Cout, Cin, K),
         or with mode=1 the (Cin', Cout', K) weight whose conv's data-gradient this is.  snake = (log-alpha, log-beta) of the input
-        (Cout <= 2 form); dsnake = (x2, log-alpha2, log-beta2): returns (y * dsnake(x2), d log-alpha, d log-beta) (Cin <= 2 form)."""
+        (Cout <= 2 form); dsnake = (x2, log-alpha2, log-beta2): returns (y * dsnake(x2), d log-alpha, d log-beta) (Cin <= 2 form); emit: as
+        conv1d_bf16x3 (Cin <= 2 form)."""
         b, cin, t = x.shape
         k = w.shape[2]
         cout = w.shape[0] if mode == 0 else w.shape[1]
@@ -223,12 +263,11 @@ class SatOps:
         y = torch.empty(b, cout, t, dtype=torch.float32, device=x.device)
         rows = self.lib.sat_edge_conv_partial_rows(b, t) if dsnake is not None else 0
         x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, rows, x.device)
-        # emit: act_next(y) as the planes of the k7 conv that reads y next (narrow-input form); this kernel takes the log-parameters themselves
-        ehi, elo, ela, elb, erows = self._emit_args(emit, b, cout, t, x.device, self._stream(x), consts=False)
+        ep, ela, elb = self._emit_args(emit, b, cout, t, x.device, self._stream(x), consts=False)     # this kernel takes the log-parameters themselves
         self._chk(self.lib.sat_edge_conv(_ptr(x), _ptr(w), _ptr(bias), _ptr(alpha), _ptr(beta), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2),
-                                         _ptr(pda), _ptr(pdb), _ptr(ehi), _ptr(elo), _ptr(ela), _ptr(elb), erows, b, cin, cout, t, k, pad, mode,
+                                         _ptr(pda), _ptr(pdb), _ptr(ep.hi), _ptr(ep.lo), _ptr(ela), _ptr(elb), ep.rows, b, cin, cout, t, k, pad, mode,
                                          int(tanh_out), self._stream(x)))
-        self._emit_done(emit, y, ehi, elo, erows)
+        self._emit_done(emit, y, ep)
         return self._dsnake_result(y, pda, pdb)
 
     def edge_conv_wgrad(self, dy, x, k, pad, snake=None, dy_rowsum=False, raw=False):
@@ -328,16 +367,16 @@ class SatOps:
             sa, sib = sconsts if sconsts is not None else self.snake_consts(snake[0], snake[1])
         y = self._conv_out(out, b, cout, tout, x.device)
         x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, rows, x.device)
-        ehi, elo, ea, eib, erows = self._emit_args(emit, b, cout, tout, x.device, self._stream(x))
+        ep, ea, eib = self._emit_args(emit, b, cout, tout, x.device, self._stream(x))
         args = (_ptr(x), _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(sa), _ptr(sib),
                 _ptr(res), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb),
                 b, cin, cout, tin, tout, *dims, int(tanh_out))
-        if emit is not None:
+        if emit:
             # plane emission (sat_conv1d_bf16x3_emit): the planes the k7 conv that consumes y next would otherwise build in a pre-pass
-            self._chk(self.lib.sat_conv1d_bf16x3_emit(*args, _ptr(ehi), _ptr(elo), _ptr(ea), _ptr(eib), erows, self._stream(x)))
+            self._chk(self.lib.sat_conv1d_bf16x3_emit(*args, _ptr(ep.hi), _ptr(ep.lo), _ptr(ea), _ptr(eib), ep.rows, self._stream(x)))
         else:
             self._chk(fn(*args, self._stream(x)))
-        self._emit_done(emit, y, ehi, elo, erows)
+        self._emit_done(emit, y, ep)
         return self._dsnake_result(y, pda, pdb)
 
     # ---- fused ResidualUnit forward (csrc/conv1d_bf16x3_k7q.h, FUSED): one launch for snake -> conv7 -> snake -> conv1 -> + x ----
@@ -361,77 +400,47 @@ class SatOps:
 
     def residual_unit_fwd(self, x, snake1, w7q, bias1, snake2, w1q, bias2, k, dil, keep_h=True, emit=None, sconsts=None):
         """y = x + conv1(snake2(conv7_dil(snake1(x)) + bias1)) + bias2 in one launch; returns (h or None, y).  w7q / w1q: pack_k7q of the
-        (C, C, K) and (C, C, 1) weights; snake1 / snake2: (log-alpha, log-beta); emit: {"snake": (la, lb) | None} -> also write the
-        next unit's activation planes (as conv1d_bf16x3(emit=...))."""
+        (C, C, K) and (C, C, 1) weights; snake1 / snake2: (log-alpha, log-beta); emit: also write the next unit's activation planes
+        (as conv1d_bf16x3(emit=...))."""
         b, c, t = x.shape
         self._f32(x, bias1, bias2)
         pad = (k - 1) * dil // 2
         st = self._stream(x)
         sa1, sib1 = sconsts[0] if sconsts is not None else self.snake_consts(snake1[0], snake1[1])
         sa2, sib2 = sconsts[1] if sconsts is not None else self.snake_consts(snake2[0], snake2[1])
-        em = self._take_emitted(x, snake1)
-        hi, lo, rows = (em["hi"], em["lo"], em["rows"]) if em is not None else self._k7_prepass(x, sa1, sib1, t, pad, st)
+        xp = self._take_emitted(x, snake1) or self._k7_prepass(x, sa1, sib1, t, pad, st)
         h = torch.empty_like(x) if keep_h else None
         y = torch.empty_like(x)
-        ehi, elo, ea, eib, erows = self._emit_args(emit, b, c, t, x.device, st, owned=False)
-        if emit is not None and ehi.data_ptr() == hi.data_ptr():
+        ep, ea, eib = self._emit_args(emit, b, c, t, x.device, st, owned=False)
+        if emit and ep.hi.data_ptr() == xp.hi.data_ptr():
             # the input planes ARE this shape's emission target (written by the previous unit): a workgroup reads halo rows its
             # neighbours' tiles would overwrite -> emit into a second buffer and alternate
-            ehi, elo, erows = self._emit_planes(b, c, t, x.device, st, alt=True)
-        self._chk(self.lib.sat_residual_unit_fwd(_ptr(hi), _ptr(lo), rows, _ptr(w7q[0]), _ptr(w7q[1]), _ptr(bias1), _ptr(sa2), _ptr(sib2),
+            ep = self._emit_planes(b, c, t, x.device, st, alt=True)
+        self._chk(self.lib.sat_residual_unit_fwd(_ptr(xp.hi), _ptr(xp.lo), xp.rows, _ptr(w7q[0]), _ptr(w7q[1]), _ptr(bias1), _ptr(sa2), _ptr(sib2),
                                                  _ptr(w1q[0]), _ptr(w1q[1]), _ptr(bias2), _ptr(x), _ptr(h), _ptr(y), b, c, t, k, dil, pad,
-                                                 _ptr(ehi), _ptr(elo), _ptr(ea), _ptr(eib), erows, st))
-        self._emit_done(emit, y, ehi, elo, erows)
+                                                 _ptr(ep.hi), _ptr(ep.lo), _ptr(ea), _ptr(eib), ep.rows, st))
+        self._emit_done(emit, y, ep)
         return h, y
 
-    def _k7_prepass(self, x, sa, sib, tout, pad, st):
-        """act(x) as the bf16 hi / lo planes a k7 conv (tout, pad) reads, by one conversion pass (sat_conv1d_k7_planes) into the shared
-        workspace — one per (device, stream), of the largest size seen: the pass and its conv are enqueued back to back on the caller's
-        current stream.  Returns (hi, lo, rows)."""
-        b, c, t = x.shape
-        rows = self.lib.sat_conv1d_k7_plane_rows(t, tout, pad)
-        need = 2 * b * ((c + 7) // 8) * rows * 8
-        ws = self._workspace(("k7p", x.device, st.value if st is not None else 0), need, torch.int16, x.device, grow=True)
-        hi, lo = ws[:need // 2], ws[need // 2:need]
-        self._chk(self.lib.sat_conv1d_k7_planes(_ptr(x), _ptr(sa), _ptr(sib), _ptr(hi), _ptr(lo), b, c, t, rows, st))
-        return hi, lo, rows
-
-    # ---- plane emission bookkeeping: producer -> the ONE k7 conv that consumes its output next ----
+    # ---- the activation planes of the k = 7 convs, and the dh that exists only as planes -------------------------------------------
+    # The k = 7 convs of the ResidualUnits (_k7_planes_call, residual_unit_fwd) read act(x) as pre-split bf16 hi / lo Planes, from one of:
+    #  * EMISSION: the producer of x wrote them in its epilogue (emit=) into the shared pair of its output shape (_emit_planes; the workspace
+    #    cache owns it) or, where the consumer owns a buffer, into that; _emitted holds them for the ONE conv that takes x next;
+    #  * the PRE-PASS (_k7_prepass): one conversion launch into the shared workspace, valid for the conv enqueued right behind it;
+    #  * the conv's OWN buffer (_owned_planes: an OwnedPlanes per SnakeBeta parameter storage, shape and device): with keep_planes the
+    #    pre-pass writes there and the conv returns the Planes, so that its backward feeds the k7 weight gradient from them and from dh's
+    #    emitted ones (conv_wgrad7_from_planes) instead of re-loading fp32, re-evaluating SnakeBeta and re-splitting in the kernel.
+    # Planes are stale (Planes.holds) for another tensor or shape, after an in-place edit of x or of a SnakeBeta parameter (torch's version
+    # counters; inference tensors have none and are never trusted) and after a rewrite of their owned buffer (gen): the forward then runs the
+    # pre-pass and the backward the fp32 weight gradient.  emit= of the producers is spelled one way: the docstring of conv1d_bf16x3.
+    # Owned buffers cost 4 bytes per element of every k7 input: +12.3 GB per batch item.  Measured peak_hbm_gib of the real step: batch 1
+    # 49.5 -> 60.97, batch 4 184.0 -> 199.86 (with the budget below; without it 229.8, where the 288 GB card's allocator thrashes and the step
+    # is 2.6x slower; profiles/wgrad7_planes/README.md).  Never evicted: a rebuilt model, an eval copy or another input length pins another set until release_owned_planes().
+    _NO_PLANES = Planes(None, None, 0)  # what a kernel gets for "no emission"
     k7_emit = True
-
-    @staticmethod
-    def _snake_key(snake):
-        return None if snake is None else (snake[0].data_ptr(), snake[1].data_ptr(), _caches.version_of(snake[0]), _caches.version_of(snake[1]))
-
-    def _note_emitted(self, y, snake, hi, lo, rows):
-        """Record that (hi, lo) hold act(y)'s planes — valid for exactly this storage, shape, activation and VERSION of y: an
-        in-place edit of y between producer and consumer (a forward hook) makes the consumer rebuild the planes.  Inference tensors
-        have no version counter, so their emission is never trusted (the consumer runs its planes pre-pass)."""
-        if not _caches.trackable(y, *(snake or ())):
-            self._emitted = None
-            return
-        self._emitted = {"ptr": y.data_ptr(), "shape": tuple(y.shape), "ver": _caches.version_of(y), "snake": self._snake_key(snake),
-                         "hi": hi, "lo": lo, "rows": rows}
-
-    def _emit_args(self, emit, b, c, t, device, st, consts=True, owned=True):
-        """emit = {"snake": (la, lb) | None} | None -> (hi, lo, a, b, rows): the planes the producer's epilogue writes act_next(y) into
-        for a (b, c, t) output y, and act_next's parameters as the kernel wants them: its constants (snake_consts), or with consts=False
-        the log-parameters as they are.  owned=False: the shared per-shape pair even where the consumer owns a buffer (the fused unit)."""
-        if emit is None:
-            return None, None, None, None, 0
-        esnake = emit.get("snake")
-        ea = eb = None
-        if esnake is not None and consts:
-            ea, eb = self.snake_consts(esnake[0], esnake[1])
-        elif esnake is not None:
-            ea, eb = esnake
-            self._f32(ea, eb)
-        hi, lo, rows = self._emit_planes(b, c, t, device, st, owner=esnake if owned else None)
-        return hi, lo, ea, eb, rows
-
-    def _emit_done(self, emit, y, hi, lo, rows):
-        if emit is not None:
-            self._note_emitted(y, emit.get("snake"), hi, lo, rows)
+    wgrad7_planes = True                # False: the pipelined fp32-input weight gradient and no owned buffers (A/B: bench.py --ops-set wgrad7_planes=0)
+    wgrad7_planes_budget_gib = 16.0     # most that all owned buffers together may hold (the flagship step, batch 1: 11.5 GiB); later convs keep the fp32 weight gradient
+    ru_k1_bwd_skip_dh = True            # sat_ru_k1_bwd stores no fp32 dh when both its consumers read dh's planes: 4 of the kernel's 16 bytes per element (A/B: --ops-set ru_k1_bwd_skip_dh=0)
 
     def emit_ok(self, cout, k, stride, tout, consumer_dil):
         """May the conv (k, stride) producing (B, cout, tout) emit planes for a k7 conv of dilation consumer_dil that reads it next?"""
@@ -445,80 +454,110 @@ class SatOps:
         return (self.k7_emit and self.use_bf16x3 and cin <= 2 and self.edge_ok(cin, cout, k, stride, dil, pad)
                 and self.k7q_applicable(cout, 7, 1, consumer_dil, 3 * consumer_dil, cout))
 
-    # ---- the k7 weight gradient from planes (csrc/conv_wgrad7_planes.h) ----
-    wgrad7_planes = True    # the ResidualUnits' k7 weight gradient reads dh's emitted planes and the planes its forward conv read (kept in a buffer
-                            # owned by that conv, 4 bytes per element of every k7 input: +12.3 GB per batch item) instead of re-loading fp32,
-                            # re-evaluating SnakeBeta and re-splitting in the kernel.  False: the pipelined kernel and the shared per-shape plane
-                            # buffers, as before (A/B: bench.py --ops-set wgrad7_planes=0; figures: profiles/wgrad7_planes/README.md)
-                            # Measured peak_hbm_gib of the real step: batch 1 49.5 -> 60.97, batch 4 184.0 -> 199.86 (with the budget below; without it
-                            # 229.8, where the 288 GB card's allocator thrashes and the step is 2.6x slower).  The buffers are keyed by the parameters'
-                            # storage and never evicted: a rebuilt or reloaded model, an eval copy or another input length pins another set until
-                            # release_owned_planes() / release_workspaces()
-    wgrad7_planes_budget_gib = 16.0     # most that all owned plane buffers together may hold: the flagship step (batch 1) needs 11.5 GiB; convs that
-                                        # come after the budget is spent keep the fp32 weight gradient
-    ru_k1_bwd_skip_dh = True    # sat_ru_k1_bwd does not store fp32 dh when both of dh's consumers (k7 weight gradient, k7q data-gradient) read
-                                # its planes: 4 of the kernel's 16 bytes per element (A/B: bench.py --ops-set ru_k1_bwd_skip_dh=0)
+    def _emit_args(self, emit, b, c, t, device, st, consts=True, owned=True):
+        """emit -> (planes, a, b): the Planes the producer's epilogue writes act_next(y) into for a (b, c, t) output y (_NO_PLANES: no emission), and
+        act_next's parameters as the kernel wants them: its constants (snake_consts), or with consts=False the log-parameters as they are.
+        owned=False: the shared per-shape pair even where the consumer owns a buffer (the fused unit)."""
+        if not emit:
+            return self._NO_PLANES, None, None
+        snake = None if emit is True else emit
+        ea, eb = (None, None) if snake is None else self.snake_consts(*snake) if consts else snake
+        self._f32(ea, eb)
+        return self._emit_planes(b, c, t, device, st, owner=snake if owned else None), ea, eb
 
-    def _owned_planes(self, snake, b, c, t, device, st, create=False):
-        """The plane buffer owned by the k7 conv whose SnakeBeta parameters are `snake` (keyed by their storage, shape and device; used from the stream that created it):
-        what that conv reads in its forward stays valid until its backward, and its address is the same every step (HIP-graph replay).
-        Zero-filled once; never created while the stream is capturing (None: the caller takes the shared buffers)."""
-        if snake is None or not self.wgrad7_planes:
-            return None
-        key = (snake[0].data_ptr(), snake[1].data_ptr(), b, c, t, device)
-        cache = self._own_planes
-        own = cache.get(key)
-        capturing = device.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        sv = st.value if st is not None else 0
-        # one stream per buffer — except a capture (its own stream, whatever the caller's): the graph is replayed on the caller's stream,
-        # in order with the eager steps that created the buffer
-        if own is not None and own["stream"] != sv and not capturing:
-            return None
-        if own is None and create:
-            if capturing:
-                return None
-            rows = self.lib.sat_conv1d_k7_plane_rows(t, t, 0)
-            n = b * ((c + 7) // 8) * rows * 8
-            held = sum(4 * o["hi"].numel() for o in cache.values())
-            if held + 4 * n > self.wgrad7_planes_budget_gib * 2 ** 30:
-                return None                                       # over the budget: this conv keeps the shared buffers and the fp32 weight gradient
-            own = {"hi": _keep_zeros(n, torch.int16, device), "lo": _keep_zeros(n, torch.int16, device), "rows": rows, "gen": 0, "stream": sv}
-            cache[key] = own
-        return own
+    def _emit_done(self, emit, y, planes):
+        """`planes` now hold act(y) — for the conv that takes y next, unless y or a parameter cannot be tracked (inference tensors)."""
+        if emit:
+            snake = None if emit is True else emit
+            self._emitted = planes.of(y, snake) if _caches.trackable(y, *(snake or ())) else None
+
+    def _take_emitted(self, x, snake, peek=False):
+        """Planes a producer emitted for exactly this tensor and activation, or None; gone afterwards, taken or not — unless peek."""
+        e = self._emitted
+        if not peek:
+            self._emitted = None
+        return e if e is not None and e.holds(x, snake) else None
 
     def _emit_planes(self, b, c, t, device, st, alt=False, owner=None):
         """Emission target for a (b, c, t) tensor: planes [b][ceil(c/8)][rows][8] with the rows around the sequence zero.  One pair
         per (shape, device, stream) (+ an alternate for the fused unit, which reads one while writing the other), zero-filled ONCE:
-        producers only ever write rows 32 .. 32 + t - 1 of existing channels."""
-        own = self._owned_planes(owner, b, c, t, device, st)        # the consumer keeps its planes for its backward (wgrad7_planes)
+        producers only ever write rows 32 .. 32 + t - 1 of existing channels.  owner (the consumer's SnakeBeta parameters): its own buffer, if any."""
+        own = self._owned_planes(owner, b, c, t, device, st)
         if own is not None:
-            own["gen"] += 1
-            return own["hi"], own["lo"], own["rows"]
+            return own.rewrite()
         rows = self.lib.sat_conv1d_k7_plane_rows(t, t, 0)          # pad 0 needs the most rows: valid for every consumer padding
         key = ("emit", b, c, t, device, st.value if st is not None else 0, alt)
         n = b * ((c + 7) // 8) * rows * 8
-        return (self._workspace(key + ("hi",), n, torch.int16, device, zero=True),
-                self._workspace(key + ("lo",), n, torch.int16, device, zero=True), rows)
+        return Planes(self._workspace(key + ("hi",), n, torch.int16, device, zero=True),
+                      self._workspace(key + ("lo",), n, torch.int16, device, zero=True), rows)
 
-    def _peek_emitted(self, x, snake):
-        """Planes a producer emitted for exactly this tensor and activation, or None; they stay for the conv that takes them next."""
-        e = self._emitted
-        if (e is not None and e["ptr"] == x.data_ptr() and e["shape"] == tuple(x.shape) and _caches.trackable(x)
-                and e["ver"] == _caches.version_of(x) and e["snake"] == self._snake_key(snake)):
-            return e
-        return None
+    def _k7_prepass(self, x, sa, sib, tout, pad, st):
+        """act(x) as the Planes a k7 conv (tout, pad) reads, by one conversion pass (sat_conv1d_k7_planes) into the shared workspace —
+        one per (device, stream), of the largest size seen: the pass and its conv are enqueued back to back on the caller's stream."""
+        b, c, t = x.shape
+        rows = self.lib.sat_conv1d_k7_plane_rows(t, tout, pad)
+        need = 2 * b * ((c + 7) // 8) * rows * 8
+        ws = self._workspace(("k7p", x.device, st.value if st is not None else 0), need, torch.int16, x.device, grow=True)
+        hi, lo = ws[:need // 2], ws[need // 2:need]
+        self._chk(self.lib.sat_conv1d_k7_planes(_ptr(x), _ptr(sa), _ptr(sib), _ptr(hi), _ptr(lo), b, c, t, rows, st))
+        return Planes(hi, lo, rows)
 
-    def _take_emitted(self, x, snake):
-        """_peek_emitted, consuming: whatever was emitted is gone afterwards, taken or not."""
-        e = self._peek_emitted(x, snake)
-        self._emitted = None
-        return e
+    def _owned_planes(self, snake, b, c, t, device, st, create=False):
+        """The OwnedPlanes of the k7 conv whose SnakeBeta parameters are `snake`: what that conv reads in its forward stays valid until its backward, at the same address
+        every step (HIP-graph replay).  Never created while the stream is capturing or past the budget (None: the shared buffers and the fp32 weight gradient)."""
+        if snake is None or not self.wgrad7_planes:
+            return None
+        key = (snake[0].data_ptr(), snake[1].data_ptr(), b, c, t, device)
+        own = self._own_planes.get(key)
+        capturing = device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        sv = st.value if st is not None else 0
+        # one stream per buffer — except a capture (its own stream, whatever the caller's): the graph is replayed on the caller's stream,
+        # in order with the eager steps that created the buffer
+        if own is not None and own.stream != sv and not capturing:
+            return None
+        if own is None and create and not capturing:
+            rows = self.lib.sat_conv1d_k7_plane_rows(t, t, 0)
+            n = b * ((c + 7) // 8) * rows * 8
+            if sum(4 * o.hi.numel() for o in self._own_planes.values()) + 4 * n <= self.wgrad7_planes_budget_gib * 2 ** 30:
+                own = self._own_planes[key] = OwnedPlanes(n, rows, device, sv)
+        return own
+
+    def release_owned_planes(self):
+        """Drop every plane buffer a k7 conv owns (after a model is discarded or reloaded, or before a pass at another input length): the next step
+        re-creates what it needs and takes the fp32 weight gradient once.  Not while a captured graph that uses them may still be replayed."""
+        self._own_planes.clear()
+
+    def kept_planes_valid(self, kept, x, snake, dil, pad):
+        """Do the Planes a k7 C -> C conv kept for its backward (conv1d_bf16x3(keep_planes=True)) still hold snake(x), and does the planes
+        weight-gradient kernel serve the shape?  Anything else keeps the fp32 kernel."""
+        b, c, t = x.shape
+        return bool(kept is not None and self.wgrad7_planes and kept.holds(x, snake) and self.conv_wgrad7_planes_ok(b, c, c, t, dil, pad, kept.rows, kept.rows))
+
+    def conv_wgrad7_from_planes(self, dh, kept, x, snake, dil, pad, raw=False):
+        """dW (C, C, 7) of the k7 conv that read `kept` = the Planes of snake(x), from them and the planes emitted for dh (slabs with raw) —
+        or None, and the caller takes the fp32 kernel: the knob is off, nothing was kept or it is stale, dh's planes were not emitted, or
+        the kernel does not serve the shape."""
+        em = self._take_emitted(dh, None, peek=True) if kept is not None and self.wgrad7_planes and kept.holds(x, snake) else None
+        b, c, t = x.shape
+        if em is None or not self.conv_wgrad7_planes_ok(b, c, c, t, dil, pad, em.rows, kept.rows):
+            return None
+        return self.conv_wgrad7_planes((em.hi, em.lo, em.rows), (kept.hi, kept.lo, kept.rows), b, c, c, t, dil, pad, raw=raw)
+
+    def _check_written(self, t):
+        """ru_k1_bwd(skip_dh=True) leaves a dh that exists only as emitted planes, marked until dh_written(): no fp32 reader may get it."""
+        if t is not None and self._dh_unwritten is not None and t.data_ptr() == self._dh_unwritten:
+            raise RuntimeError("this tensor is a dh that sat_ru_k1_bwd did not write (skip_dh): only its planes exist")
+
+    def dh_written(self):
+        """The backward that skipped a dh store is over: its address means nothing any more."""
+        self._dh_unwritten = None
 
     def conv1d_bf16x3(self, x, w_planes, cout, k, stride=1, dil=1, pad=0, tout=None, bias=None, snake=None, res=None,
-                      tanh_out=False, dsnake=None, out=None, sconsts=None, emit=None, keep_planes=None):
+                      tanh_out=False, dsnake=None, out=None, sconsts=None, emit=None, keep_planes=False):
         """Same contract as conv1d; `snake` = (log-alpha, log-beta) as everywhere else; sconsts = snake_consts(*snake) if the
-        caller keeps them (frozen layers).  keep_planes (a dict, q-packed k7 convs only): a backward will follow — the planes are read from
-        the buffer this conv owns (_owned_planes) and keep_planes["kept"] tells the backward where they are and what makes them stale."""
+        caller keeps them (frozen layers).  emit: None / False — nothing | True | (log-alpha, log-beta) — also write y (or snake(y)) as the Planes
+        of the k7 conv that reads it next.  keep_planes=True (a backward will follow): returns (y, kept) — a plane-fed k7 C -> C conv then reads its
+        planes from the buffer it owns and `kept` is their handle for conv_wgrad7_from_planes; None where nothing was kept."""
         b, cin, tin = x.shape
         if tout is None:
             tout = (tin + 2 * pad - dil * (k - 1) - 1) // stride + 1
@@ -527,44 +566,36 @@ class SatOps:
             if not (stride == 1 and 5 <= k <= 7 and 0 <= pad <= 32 and (k - 1) * dil <= 62):
                 raise ValueError("conv1d_bf16x3: q-packed weights need stride 1, 5 <= K <= 7, pad <= 32, (K-1)*dil <= 62")
             return self._k7_planes_call(rows, x, w_planes, cout, tout, k, dil, pad, bias, snake, res, tanh_out, dsnake, out, sconsts, keep_planes)
-        return self._bf16x3_call(self.lib.sat_conv1d_bf16x3, rows, x, w_planes, cout, tout, (k, stride, dil, pad),
-                                 bias, snake, res, tanh_out, dsnake, out, sconsts, emit)
+        y = self._bf16x3_call(self.lib.sat_conv1d_bf16x3, rows, x, w_planes, cout, tout, (k, stride, dil, pad),
+                              bias, snake, res, tanh_out, dsnake, out, sconsts, emit)
+        return (y, None) if keep_planes else y
 
-    # the k = 7 convs of the ResidualUnits read their (activated) input as pre-split bf16 planes: written by the producer's epilogue
-    # (plane emission) or by one conversion pass per conv (_k7_prepass) instead of one per workgroup.
     def _k7_planes_call(self, prows, x, w_planes, cout, tout, k, dil, pad, bias, snake, res, tanh_out, dsnake, out=None, sconsts=None,
-                        keep_planes=None):
+                        keep_planes=False):
         b, cin, tin = x.shape
         self._f32(x, bias, res)
         sa = sib = None
         if snake is not None:
             sa, sib = sconsts if sconsts is not None else self.snake_consts(snake[0], snake[1])
         st = self._stream(x)
-        em = self._take_emitted(x, snake)
-        # keep_planes (ResidualUnitFn.forward, when a backward will follow): the planes live in the buffer this conv owns, and the
-        # handle says what makes them stale: a rewrite of the buffer, another x, edited parameters
-        keep = keep_planes is not None
-        if em is None:
+        xp = self._take_emitted(x, snake)               # the producer's epilogue already wrote act(x) as planes
+        if xp is None:
             self._check_written(x)
-        own = self._owned_planes(snake, b, cin, tin, x.device, st, create=True) if keep and tin == tout and _caches.trackable(x) else None
-        if own is not None and em is None:
-            hi, lo, rows = own["hi"], own["lo"], own["rows"]
-            own["gen"] += 1
-            self._chk(self.lib.sat_conv1d_k7_planes(_ptr(x), _ptr(sa), _ptr(sib), _ptr(hi), _ptr(lo), b, cin, tin, rows, st))
-        if own is not None and (em is None or em["hi"].data_ptr() == own["hi"].data_ptr()):
-            # (emitted into a shared buffer — the first step, before this conv owned one: the backward keeps the fp32 path this once)
-            keep_planes["kept"] = {"buf": own, "gen": own["gen"], "ptr": x.data_ptr(), "shape": tuple(x.shape), "ver": _caches.version_of(x),
-                             "snake": self._snake_key(snake)}
-        if em is not None:
-            hi, lo, rows = em["hi"], em["lo"], em["rows"]          # the producer's epilogue already wrote act(x) as planes
-        elif own is None:
-            hi, lo, rows = self._k7_prepass(x, sa, sib, tout, pad, st)
+        own = self._owned_planes(snake, b, cin, tin, x.device, st, create=True) if keep_planes and tin == tout and _caches.trackable(x) else None
+        if xp is None and own is not None:
+            xp = own.rewrite().of(x, snake)
+            self._chk(self.lib.sat_conv1d_k7_planes(_ptr(x), _ptr(sa), _ptr(sib), _ptr(xp.hi), _ptr(xp.lo), b, cin, tin, xp.rows, st))
+        elif xp is None:
+            xp = self._k7_prepass(x, sa, sib, tout, pad, st)
+        # only the k7 C -> C weight gradient reads kept planes, and only from the owned buffer (the first step's are emitted into a shared one: fp32 this once)
+        kept = xp if own is not None and xp.own is own and k == 7 and cout == cin else None
         y = self._conv_out(out, b, cout, tout, x.device)
         x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, prows, x.device)
-        self._chk(self.lib.sat_conv1d_bf16x3_planesq(_ptr(hi), _ptr(lo), rows, _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(res),
+        self._chk(self.lib.sat_conv1d_bf16x3_planesq(_ptr(xp.hi), _ptr(xp.lo), xp.rows, _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(res),
                                                      _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb), b, cin, cout, tin, tout,
                                                      k, dil, pad, int(tanh_out), {True: 0, False: 1, "force": 2}[self.k7q_persist] | (4 if self.k7q_dma_in_mfma else 0), st))
-        return self._dsnake_result(y, pda, pdb)
+        y = self._dsnake_result(y, pda, pdb)
+        return (y, kept) if keep_planes else y
 
     def convtr1d_bf16x3(self, x, w_planes, cout, k, stride, pad, tout=None, bias=None, snake=None, res=None,
                         tanh_out=False, dsnake=None, sconsts=None):
@@ -639,9 +670,9 @@ class SatOps:
 
     def ru_k1_bwd(self, dy, h, w2, snake2, emit=False, wt=None, raw=False, skip_dh=False):
         """Backward of y = x + conv1x1(snake2(h)) w.r.t. everything but x, in one launch: returns (dh, dlog_alpha2, dlog_beta2, dW2 (C, C, 1),
-        dbias2 (C,), dbias1 (C,) = sum dh).  emit=True also writes dh as the activation planes of the k7 data-gradient that consumes it
-        next (as conv1d_bf16x3(emit={"snake": None})).  raw=True: dW2 as WgradSlabs (for wn_grad_splits).  skip_dh (needs emit): the returned
-        dh is allocated but NOT written — only its planes are; for a caller whose consumers of dh all read the planes."""
+        dbias2 (C,), dbias1 (C,) = sum dh).  emit=True also writes dh as the Planes of the k7 data-gradient that consumes it next (as
+        conv1d_bf16x3(emit=True)).  raw=True: dW2 as WgradSlabs (for wn_grad_splits).  skip_dh (needs emit): the returned dh is allocated but
+        NOT written — only its planes are; for a caller whose consumers of dh all read the planes, and says dh_written() after them."""
         b, c, t = dy.shape
         a2, b2 = snake2
         self._f32(dy, h, w2, a2, b2)
@@ -653,19 +684,15 @@ class SatOps:
         dh = torch.empty_like(dy)
         slabs = torch.empty(ns, c * c, dtype=torch.float32, device=dy.device)
         part = torch.empty(4 * c, ns, dtype=torch.float32, device=dy.device)
-        ehi = elo = None
-        erows = 0
-        if emit:
-            ehi, elo, erows = self._emit_planes(b, c, t, dy.device, st)
-        if skip_dh and not emit:
-            raise ValueError("ru_k1_bwd: skip_dh needs emit=True")
+        if emit not in (None, False, True) or (skip_dh and not emit):
+            raise ValueError("ru_k1_bwd: emit is True or nothing (dh has no activation), and skip_dh needs emit=True")
+        ep = self._emit_planes(b, c, t, dy.device, st) if emit else self._NO_PLANES
         self._dh_unwritten = dh.data_ptr() if skip_dh else None
         self._chk(self.lib.sat_ru_k1_bwd(_ptr(dy), _ptr(h), _ptr(wt_hi), _ptr(wt_lo), _ptr(a2), _ptr(b2), None if skip_dh else _ptr(dh),
-                                         _ptr(ehi), _ptr(elo), erows, _ptr(slabs), _ptr(part), b, c, t, st))
-        if emit:
-            self._note_emitted(dh, None, ehi, elo, erows)
-            if skip_dh and self._emitted is None:
-                raise RuntimeError("ru_k1_bwd: dh was skipped but its planes cannot be tracked")
+                                         _ptr(ep.hi), _ptr(ep.lo), ep.rows, _ptr(slabs), _ptr(part), b, c, t, st))
+        self._emit_done(emit, dh, ep)
+        if skip_dh and self._emitted is None:
+            raise RuntimeError("ru_k1_bwd: dh was skipped but its planes cannot be tracked")
         dw2 = WgradSlabs(slabs, ns, (c, c, 1), (c, 1, 1))
         if not raw:
             dw2 = dw2.reduce(self)
@@ -694,32 +721,8 @@ class SatOps:
                                                   b, m, n, t, dil, pad, _ptr(rs), self._stream(dy)))
         return self._wgrad_result(WgradSlabs(partial, nsplit, (m, n, 7), (n, 1, m * n)), raw, dy, dy_rowsum, rs)
 
-    def _check_written(self, t):
-        """A dh whose fp32 store ru_k1_bwd(skip_dh=True) skipped exists only as planes: reading it as fp32 is a bug, not a fallback."""
-        if t is not None and self._dh_unwritten is not None and t.data_ptr() == self._dh_unwritten:
-            raise RuntimeError("this tensor is a dh that sat_ru_k1_bwd did not write (skip_dh): only its planes exist")
-
-    def dh_written(self):
-        """The backward that skipped a dh store is over: its address means nothing any more."""
-        self._dh_unwritten = None
-
-    def release_owned_planes(self):
-        """Drop every plane buffer a k7 conv owns (wgrad7_planes): after a model is discarded or reloaded, or before a pass at another
-        input length.  The next training step re-creates what it needs (its first backward takes the fp32 weight-gradient kernel where
-        the planes were emitted before the buffer existed).  Not while a captured graph that uses them may still be replayed."""
-        self._own_planes.clear()
-
     def conv_wgrad7_planes_ok(self, b, m, n, t, dil, pad, rows_dy, rows_act):
         return self.use_bf16x3 and self.wgrad7_planes and self.lib.sat_conv_wgrad7_planes_ok(b, m, n, t, dil, pad, rows_dy, rows_act) == 1
-
-    def kept_planes_valid(self, kp, x, snake, dil, pad):
-        """Are the planes a k7 C -> C conv kept for its backward (kp = keep_planes["kept"], _k7_planes_call) still what its forward read —
-        the owned buffer not rewritten since, the same x (storage, shape, version), the same parameters — and does the planes
-        weight-gradient kernel serve the shape?  Anything else keeps the fp32 kernel."""
-        b, c, t = x.shape
-        return bool(self.wgrad7_planes and kp["gen"] == kp["buf"]["gen"] and kp["ptr"] == x.data_ptr() and kp["shape"] == tuple(x.shape)
-                    and kp["ver"] == _caches.version_of(x) and kp["snake"] == self._snake_key(snake)
-                    and self.conv_wgrad7_planes_ok(b, c, c, t, dil, pad, kp["buf"]["rows"], kp["buf"]["rows"]))
 
     def conv_wgrad7_planes(self, dy_planes, act_planes, b, m, n, t, dil, pad, raw=False):
         """dW (Cout, Cin, 7) as conv_wgrad7_bf16x3, both operands as (hi, lo, rows) planes: dy's and act(x)'s (sat_conv1d_k7_planes layout)."""

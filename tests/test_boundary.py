@@ -140,7 +140,7 @@ def test_vae_inference_mode_gpu(hip):
 
 
 def _emitted_planes_follow_in_place_edits(device, ops):
-    """The producer -> consumer plane side channel (ops._note_emitted / _take_emitted) is valid for ONE version of the producer's
+    """The producer -> consumer plane side channel (ops._emit_done / _take_emitted) is valid for ONE version of the producer's
     output: a forward hook that edits it in place must make the consuming k7 conv rebuild its planes (it used to
     multiply the OLD values while the residual added the new ones)."""
     from stable_audio_tools_amd.autoencoders import EncoderBlock

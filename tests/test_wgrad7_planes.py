@@ -153,11 +153,12 @@ def test_wgrad7_planes_contract(emu):
 
 
 # ---------------------------------------------------------------- ResidualUnitFn end to end
-def _unit(ops, dev, c, t, dil, steps=2, recompute=False, stale=None):
+def _unit(ops, dev, c, t, dil, steps=2, recompute=False, stale=None, on_forward=None):
     """Gradients of `steps` forward / backward passes of one unit (the second one finds the owned plane buffer in place).
     stale (last pass only): "gen" — the same unit runs a second forward before the backward (its owned buffer is rewritten);
     "ver" / "snake" — the kept handle's record of x's version / of the SnakeBeta parameters no longer matches (what an in-place edit
-    between forward and backward leaves behind; autograd itself refuses such an edit of a saved tensor, so the guard is driven directly)."""
+    between forward and backward leaves behind; autograd itself refuses such an edit of a saved tensor, so the guard is driven directly).
+    on_forward(y): called after every forward."""
     g = torch.Generator().manual_seed(3)
     mk = lambda *s, sc=1.0: (sc * torch.randn(*s, generator=g)).to(dev).requires_grad_(True)
     x = mk(2, c, t)
@@ -171,17 +172,19 @@ def _unit(ops, dev, c, t, dil, steps=2, recompute=False, stale=None):
         for p in leaves:
             p.grad = None
         y = F_.ResidualUnitFn.apply(x, a1, b1, w1, bias1, a2, b2, w2, bias2, dil, ops, recompute)
+        if on_forward is not None:
+            on_forward(y)
         if stale is not None and _ == steps - 1:
             kp = y.grad_fn.k7_planes
             assert kp is not None, "nothing was kept: the guard is not exercised"
             if stale == "gen":
                 with torch.no_grad():
                     F_.ResidualUnitFn.apply(x.detach().flip(2).requires_grad_(True), a1, b1, w1, bias1, a2, b2, w2, bias2, dil, ops, recompute)
-                assert kp["gen"] != kp["buf"]["gen"]
+                assert kp.gen != kp.own.gen
             elif stale == "ver":
-                kp["ver"] -= 1
+                kp.ver -= 1
             else:
-                kp["snake"] = kp["snake"][:2] + (kp["snake"][2] - 1,) + kp["snake"][3:]
+                kp.snake = kp.snake[:2] + (kp.snake[2] - 1,) + kp.snake[3:]
         y.backward(dy)
         out = [p.grad.clone() for p in leaves]
     return out
@@ -252,6 +255,28 @@ def test_residual_unit_outside_contract_sim(emu):
         on = _unit(emu, "cpu", 64, 192, 9)
     finally:
         emu.wgrad7_planes = saved
+    for a, b in zip(on, ref):
+        assert torch.equal(a, b)
+
+
+def test_residual_unit_planes_budget_spent_sim(emu):
+    """wgrad7_planes_budget_gib = 0: no conv comes to own a plane buffer — nothing is kept, the planes kernel never runs and every
+    gradient is the fp32 kernel's, bit for bit."""
+    saved = (emu.wgrad7_planes, emu.wgrad7_planes_budget_gib)
+    calls, kept = [], []
+    orig = emu.conv_wgrad7_planes
+    emu.conv_wgrad7_planes = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
+    try:
+        emu.wgrad7_planes = False
+        ref = _unit(emu, "cpu", 128, 128, 3)
+        emu.wgrad7_planes, emu.wgrad7_planes_budget_gib = True, 0
+        emu.release_owned_planes()
+        on = _unit(emu, "cpu", 128, 128, 3, on_forward=lambda y: kept.append(y.grad_fn.k7_planes))
+    finally:
+        del emu.conv_wgrad7_planes
+        emu.wgrad7_planes, emu.wgrad7_planes_budget_gib = saved
+    assert kept == [None, None], kept
+    assert not calls, "conv_wgrad7_planes ran although no conv owns a buffer"
     for a, b in zip(on, ref):
         assert torch.equal(a, b)
 

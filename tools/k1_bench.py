@@ -40,7 +40,7 @@ for li in ([int(a) for a in sys.argv[1:]] or range(len(LEVELS))):
     s3 = (torch.randn(c, device=dev) * 0.2, torch.randn(c, device=dev) * 0.2)
     pf, pd = o.pack_bf16x3(w), o.pack_bf16x3(w, mode=1)
     c2 = o.snake_consts(*s2)
-    emit = {"snake": s3} if o.emit_ok(c, 1, 1, t, 1) else None
+    emit = s3 if o.emit_ok(c, 1, 1, t, 1) else None
     flops = 2.0 * c * c * t
     kinds = {
         "fwd": (lambda: o.conv1d_bf16x3(h, pf, c, 1, 1, 1, 0, bias=bias, snake=s2, res=x, sconsts=c2, emit=emit), 4.0 * c * t * (4 if emit else 3)),

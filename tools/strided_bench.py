@@ -49,7 +49,7 @@ for li in want:
     p_up = o.pack_bf16x3(w_up, mode=2, stride=s)
     p_up_d = o.pack_bf16x3(w_up, stride=s)
     cx, cz = o.snake_consts(*sx), o.snake_consts(*sz)
-    emit = {"snake": sz} if o.emit_ok(co, k, s, tout, 1) else None
+    emit = sz if o.emit_ok(co, k, s, tout, 1) else None
     flops = 2.0 * co * ci * k * tout
     kinds = {
         "down_fwd": (lambda: o.conv1d_bf16x3(x, p_dn, co, k, s, 1, pad, bias=b_dn, snake=sx, sconsts=cx, emit=emit), 4.0 * (ci * tin + co * tout)),
