@@ -206,6 +206,12 @@ int sat_conv_wgrad7_planes_nsplit(int B, int M, int N, int T);
 int sat_conv_wgrad7_planes(const short* dy_hi, const short* dy_lo, int rows_dy, const short* act_hi, const short* act_lo, int rows_act,
                            float* partial, long long so_m, long long so_n, long long so_k, int B, int M, int N, int T, int dil, int pad,
                            void* stream);
+/* The same with the kernel variant chosen by the caller (A/B arms; sat_conv_wgrad7_planes forwards with the shipped default, 2):
+ * 2 = v_mfma_f32_16x16x32_bf16 (sums over time in groups of 32 steps), 0 = v_mfma_f32_32x32x16_bf16 (groups of 16: the results differ in
+ * the last bits).  Any other value is an error and nothing is launched. */
+int sat_conv_wgrad7_planes_v(const short* dy_hi, const short* dy_lo, int rows_dy, const short* act_hi, const short* act_lo, int rows_act,
+                             float* partial, long long so_m, long long so_n, long long so_k, int B, int M, int N, int T, int dil, int pad,
+                             int variant, void* stream);
 /* Test probe of the transposed LDS read: one wave, image = 1024 16-bit elements copied to LDS, lane l reads at byte offset lane_off[l]
  * (8-byte aligned, <= 2040), out[4 l + q] = its element q. */
 int sat_lds_read_tr16_probe(const short* image, const int* lane_off, short* out, void* stream);

@@ -57,6 +57,7 @@ SIGNATURES = {
     "sat_conv_wgrad7_planes_ok": (_I, [_I] * 8),
     "sat_conv_wgrad7_planes_nsplit": (_I, [_I] * 4),
     "sat_conv_wgrad7_planes": (_I, [_P, _P, _I, _P, _P, _I, _P] + [_L] * 3 + [_I] * 6 + [_P]),
+    "sat_conv_wgrad7_planes_v": (_I, [_P, _P, _I, _P, _P, _I, _P] + [_L] * 3 + [_I] * 7 + [_P]),
     "sat_lds_read_tr16_probe": (_I, [_P] * 4),
     "sat_conv_wgrad_bf16x3": (_I, [_P] * 4 + [_I, _P] + [_L] * 3 + [_I] * 8 + [_P, _P]),
     "sat_conv_wgrad_bf16x3_nsplit": (_I, [_I] * 6),

@@ -345,10 +345,21 @@ extern "C" int sat_conv_wgrad7_planes_nsplit(int B, int M, int N, int T) {
 }
 // sat_conv_wgrad7_bf16x3 with both operands as planes: dy_hi / dy_lo = split(dy), act_hi / act_lo = split(act(x)) (conv1d_planes.h).
 // Writes sat_conv_wgrad7_planes_nsplit slabs (element (m, n, k) at m*so_m + n*so_n + k*so_k, slab stride M*N*7).
-extern "C" int sat_conv_wgrad7_planes(const short* dy_hi, const short* dy_lo, int rows_dy, const short* act_hi, const short* act_lo,
-                                      int rows_act, float* partial, long long so_m, long long so_n, long long so_k, int B, int M, int N,
-                                      int T, int dil, int pad, void* stream) {
+// variant: 2 = M16 (16x16x32 MFMAs, the shipped form), 0 = 32x32x16 (the A/B arm) — conv_wgrad7_planes.h.  Bit 1 is M16; bit 0 was the
+// LDS-DMA placement that did not ship (profiles/wgrad7_planes_variants/README.md), so 1 and 3 are refused like anything outside 0 .. 3.
+// One default for every level: M16 is faster at all four level shapes and all three dilations (the README's table).
+#define SAT_WGPL_DEFAULT_VARIANT 2
+template <bool M16>
+static void sat_wgpl_launch(int dil, dim3 grid, void* stream, const SatWgPlParams& p) {
+    if (dil == 1) SAT_LAUNCH((sat_wgrad7_planes_kernel<1, M16>), grid, dim3(SAT_WQ_NT), stream, p);
+    else if (dil == 3) SAT_LAUNCH((sat_wgrad7_planes_kernel<3, M16>), grid, dim3(SAT_WQ_NT), stream, p);
+    else SAT_LAUNCH((sat_wgrad7_planes_kernel<9, M16>), grid, dim3(SAT_WQ_NT), stream, p);
+}
+extern "C" int sat_conv_wgrad7_planes_v(const short* dy_hi, const short* dy_lo, int rows_dy, const short* act_hi, const short* act_lo,
+                                        int rows_act, float* partial, long long so_m, long long so_n, long long so_k, int B, int M, int N,
+                                        int T, int dil, int pad, int variant, void* stream) {
     if (!dy_hi || !dy_lo || !act_hi || !act_lo || !partial) { sat_set_error("sat_conv_wgrad7_planes: missing buffer"); return 1; }
+    if (variant != 0 && variant != 2) { sat_set_error("sat_conv_wgrad7_planes_v: variant must be 0 or 2"); return 1; }
     if (!sat_conv_wgrad7_planes_ok(B, M, N, T, dil, pad, rows_dy, rows_act)) {
         sat_set_error("sat_conv_wgrad7_planes: shape outside the kernel's contract (sat_conv_wgrad7_planes_ok)");
         return 1;
@@ -359,10 +370,15 @@ extern "C" int sat_conv_wgrad7_planes(const short* dy_hi, const short* dy_lo, in
     SatWgPlParams p{dy_hi, dy_lo, act_hi, act_lo, partial, (long long)M * N * 7, so_m, so_n, so_k, B, M, N, T, pad, rows_dy, rows_act,
                     sat_cdiv(M, 8), sat_cdiv(N, 8), pl.cps, pl.nchunks, pl.nT};
     dim3 grid(sat_cdiv(M, SAT_CO_T), sat_cdiv(N, SAT_WQ_NI), pl.nsplit);
-    if (dil == 1) SAT_LAUNCH((sat_wgrad7_planes_kernel<1>), grid, dim3(SAT_WQ_NT), stream, p);
-    else if (dil == 3) SAT_LAUNCH((sat_wgrad7_planes_kernel<3>), grid, dim3(SAT_WQ_NT), stream, p);
-    else SAT_LAUNCH((sat_wgrad7_planes_kernel<9>), grid, dim3(SAT_WQ_NT), stream, p);
+    if (variant == 2) sat_wgpl_launch<true>(dil, grid, stream, p);
+    else sat_wgpl_launch<false>(dil, grid, stream, p);
     return sat_check_launch("sat_conv_wgrad7_planes");
+}
+extern "C" int sat_conv_wgrad7_planes(const short* dy_hi, const short* dy_lo, int rows_dy, const short* act_hi, const short* act_lo,
+                                      int rows_act, float* partial, long long so_m, long long so_n, long long so_k, int B, int M, int N,
+                                      int T, int dil, int pad, void* stream) {
+    return sat_conv_wgrad7_planes_v(dy_hi, dy_lo, rows_dy, act_hi, act_lo, rows_act, partial, so_m, so_n, so_k, B, M, N, T, dil, pad,
+                                    SAT_WGPL_DEFAULT_VARIANT, stream);
 }
 
 // =====================================================================================================================

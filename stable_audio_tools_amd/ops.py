@@ -439,6 +439,7 @@ class SatOps:
     _NO_PLANES = Planes(None, None, 0)  # what a kernel gets for "no emission"
     k7_emit = True
     wgrad7_planes = True                # False: the pipelined fp32-input weight gradient and no owned buffers (A/B: bench.py --ops-set wgrad7_planes=0)
+    wgrad7_planes_variant = 2           # sat_wgrad7_planes_kernel: 2 = 16x16x32 MFMAs (shipped), 0 = 32x32x16, the A/B arm (bench.py --ops-set wgrad7_planes_variant=0; profiles/wgrad7_planes_variants/README.md)
     wgrad7_planes_budget_gib = 16.0     # most that all owned buffers together may hold (the flagship step, batch 1: 11.5 GiB); later convs keep the fp32 weight gradient
     ru_k1_bwd_skip_dh = True            # sat_ru_k1_bwd stores no fp32 dh when both its consumers read dh's planes: 4 of the kernel's 16 bytes per element (A/B: --ops-set ru_k1_bwd_skip_dh=0)
 
@@ -732,8 +733,8 @@ class SatOps:
             raise RuntimeError("conv_wgrad7_planes: shape not served by the planes kernel (conv_wgrad7_planes_ok)")
         nsplit = self.lib.sat_conv_wgrad7_planes_nsplit(b, m, n, t)
         partial = torch.empty(nsplit, m * n * 7, dtype=torch.float32, device=dhi.device)
-        self._chk(self.lib.sat_conv_wgrad7_planes(_ptr(dhi), _ptr(dlo), drows, _ptr(ahi), _ptr(alo), arows, _ptr(partial), n, 1, m * n,
-                                                  b, m, n, t, dil, pad, self._stream(dhi)))
+        self._chk(self.lib.sat_conv_wgrad7_planes_v(_ptr(dhi), _ptr(dlo), drows, _ptr(ahi), _ptr(alo), arows, _ptr(partial), n, 1, m * n,
+                                                    b, m, n, t, dil, pad, self.wgrad7_planes_variant, self._stream(dhi)))
         slabs = WgradSlabs(partial, nsplit, (m, n, 7), (n, 1, m * n))       # tap-major, as conv_wgrad7_bf16x3
         return slabs if raw else slabs.reduce(self)
 

@@ -1,5 +1,5 @@
 """Run ONE conv configuration a few times (for rocprofv3 --pmc runs).  usage: pmc_conv.py <kind> [C] [T]
-kind: conv7 | conv7q | conv7ns | dgrad7 | conv1 | wgrad7 | wgrad1 | wgrads2 | wgrads8 | ruk1 | disc9 | calib"""
+kind: conv7 | conv7q | conv7ns | dgrad7 | conv1 | wgrad7 | wgrad7pV (the planes kernel, variant V = 0..3, dilation 9) | wgrad1 | wgrads2 | wgrads8 | ruk1 | disc9 | calib"""
 import os
 import sys
 
@@ -49,6 +49,18 @@ elif kind == "conv1":
     fn = lambda: ops.conv1d_bf16x3(x, pl, C, 1, 1, 1, 0, bias=bias, snake=(la, lb), res=x)
 elif kind == "wgrad7":
     fn = lambda: ops.conv_wgrad7_bf16x3(dy, x, 9, 27, snake=(la, lb))
+elif kind.startswith("wgrad7p"):   # csrc/conv_wgrad7_planes.h, the planes built once outside the launches
+    import ctypes
+    ops.wgrad7_planes_variant = int(kind[7:] or 0)
+    planes = []
+    for src, sn in ((dy, None), (x, (la, lb))):
+        rows = ops.lib.sat_conv1d_k7_plane_rows(T, T, 0)
+        hi, lo = torch.zeros(2, (C // 8) * rows * 8, dtype=torch.int16, device=dev).unbind(0)
+        sa, sib = ops.snake_consts(*sn) if sn is not None else (None, None)
+        ptr = lambda v: None if v is None else ctypes.c_void_p(v.data_ptr())
+        assert ops.lib.sat_conv1d_k7_planes(ptr(src), ptr(sa), ptr(sib), ptr(hi), ptr(lo), 1, C, T, rows, None) == 0
+        planes.append((hi, lo, rows))
+    fn = lambda: ops.conv_wgrad7_planes(planes[0], planes[1], 1, C, C, T, 9, 27, raw=True)
 elif kind == "wgrad1":
     fn = lambda: ops.conv_wgrad(dy, x, 1, 1, 1, 0, snake=(la, lb), snake_on=2)
 elif kind in ("wgrads2", "wgrads8"):
