@@ -61,6 +61,8 @@ struct SatConvBfLaunch {
     float* ru_h = nullptr;
 };
 
+#include "conv_epilogue.h"        // the output epilogue of this file's kernel and of the k7 / k7q ones
+
 SAT_DEVICE void sat_split2(float x, short* hi, short* lo) {
     const short h = sat_f32_to_bf16(x);
     *hi = h;
@@ -348,118 +350,9 @@ sat_conv1d_bf16x3_kernel(SatConvBfLaunch a) {
     const bool vec4 = so == 0 && a.out_shift == 0 && (p.Tout & 3) == 0 &&
                       (((uintptr_t)p.y | (uintptr_t)p.x2 | (uintptr_t)p.res) & 15) == 0;
     if (vec4) {
-        // 16-byte epilogue (plain output addressing): each wave transposes its accumulators through LDS so that a lane
-        // owns 4 consecutive time steps of a row; the x2 / res loads of a 32-row half are all issued before use.
-        if (!bwd) __syncthreads();                          // the K loop's slabs are free (bwd synchronised above)
-        float (*tile)[68] = reinterpret_cast<float (*)[68]>(lds_pool) + wave * 32;
-        const int lr = lane >> 4, t4 = (lane & 15) * 4;    // this lane's row within a group of 4, its 4 time steps
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-            const bool half_on = wave_on && (mi == 0 || mi1_on);
-            if (mi == 1) __syncthreads();                   // every wave is done reading its first half
-            if (half_on) {
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) tile[(r & 3) + 8 * (r >> 2) + 4 * hi][ni * 32 + l31] = acc[mi][ni][r];
-            }
-            __syncthreads();                                // (a wave only reads its own tile: this orders its own lanes)
-            if (half_on) {
-                const int tg = t0 + t_w + t4;
-                f32x4 xv[8], rv[8];
-                if (co0 + SAT_CO_T <= p.Cout && t0 + SAT_T_T <= p.Tout) {
-                    // a tile fully inside the tensor (block-uniform): the loads go out back to back, none wrapped in its own branch
-                    const size_t o0 = ((size_t)b * p.Cout + co0 + co_w + mi * 32 + lr) * p.Tout + tg;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        xv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                        rv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                        if (bwd) xv[j] = *reinterpret_cast<const f32x4*>(p.x2 + o0 + (size_t)(j * 4) * p.Tout);
-                        if (p.res) rv[j] = *reinterpret_cast<const f32x4*>(p.res + o0 + (size_t)(j * 4) * p.Tout);
-                    }
-                } else
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int co = co0 + co_w + mi * 32 + j * 4 + lr;
-                    const bool ok = co < p.Cout && tg < p.Tout;
-                    const size_t o = ((size_t)b * p.Cout + (ok ? co : 0)) * p.Tout + (ok ? tg : 0);
-                    xv[j] = (bwd && ok) ? *reinterpret_cast<const f32x4*>(p.x2 + o) : f32x4{0.f, 0.f, 0.f, 0.f};
-                    rv[j] = (p.res && ok) ? *reinterpret_cast<const f32x4*>(p.res + o) : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int row = j * 4 + lr;
-                    const int col = co_w + mi * 32 + row;
-                    const int co = co0 + col;
-                    const bool ok = co < p.Cout && tg < p.Tout;
-                    const f32x4 av = *reinterpret_cast<const f32x4*>(&tile[row][t4]);
-                    const float bias = ep_lds[0][col];
-                    const float a2 = ep_lds[1][col], b2 = ep_lds[2][col];
-                    float pda = 0.f, pdb = 0.f;
-                    f32x4 ov;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = av[e] + bias;
-                        if (bwd) {
-                            const SatSnakeGrad g = sat_snake_grad(xv[j][e], a2, b2);
-                            pda += v * g.dla;
-                            pdb += v * g.dlb;
-                            v *= g.dx;
-                        }
-                        v += rv[j][e];
-                        if (p.tanh_out) v = tanhf(v);
-                        ov[e] = v;
-                    }
-                    if (ok) *reinterpret_cast<f32x4*>(p.y + ((size_t)b * p.Cout + co) * p.Tout + tg) = ov;
-                    if (a.em_hi) {
-                        // plane emission, step 1: the consumer's activation of the finished values goes back into this lane's own
-                        // cell of the transposition tile (rows past Cout hold act(0) = 0)
-                        f32x4 ev = ov;
-                        if (a.em_a) {
-                            const float ea = ep_lds[3][col], eib = ep_lds[4][col];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) ev[e] = sat_snake(ov[e], ea, eib);
-                        }
-                        if (!ok) ev = f32x4{0.f, 0.f, 0.f, 0.f};
-                        *reinterpret_cast<f32x4*>(&tile[row][t4]) = ev;
-                    }
-                    if (bwd) {
-                        if (!ok) { pda = 0.f; pdb = 0.f; }
-#pragma unroll
-                        for (int m = 8; m >= 1; m >>= 1) {     // sum over the 16 lanes that share this row
-                            pda += __shfl_xor(pda, m);
-                            pdb += __shfl_xor(pdb, m);
-                        }
-                        if ((lane & 15) == 0) {
-                            red_lds[0][wave & 1][col] = pda;
-                            red_lds[1][wave & 1][col] = pdb;
-                        }
-                    }
-                }
-                if (a.em_hi) {
-                    // step 2: read the tile COLUMN-wise — an item is 8 consecutive channels of one time step = one 16-byte plane
-                    // row — split and store: 64 lanes write 1 KiB of each plane contiguously (the wave's LDS ops execute in order)
-                    sat_wave_sync();
-#pragma unroll
-                    for (int it = 0; it < 4; ++it) {
-                        const int tt = lane, g = it;
-                        const int c8i = ((co0 + co_w + mi * 32) >> 3) + g;
-                        const int tq = t0 + t_w + tt;
-                        float v8[8];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v8[e] = tile[g * 8 + e][tt];
-                        uint32_t h[4], l[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) sat_split2_pk(v8[2 * e], v8[2 * e + 1], &h[e], &l[e]);
-                        if (c8i < a.em_c8 && tq < p.Tout) {
-                            const size_t o = (((size_t)b * a.em_c8 + c8i) * a.em_rows + SAT_K7P_LEAD_ROWS + tq) * 8;
-                            *reinterpret_cast<u32x4*>(a.em_hi + o) = u32x4{h[0], h[1], h[2], h[3]};
-                            *reinterpret_cast<u32x4*>(a.em_lo + o) = u32x4{l[0], l[1], l[2], l[3]};
-                        }
-                    }
-                }
-            }
-        }
+        // plain output addressing: the 16-byte epilogue (conv_epilogue.h), with plane emission
+        const SatConvEpArgs ta = sat_conv_ep_args(&a, p.y, p.res, true, b, co0, t0, t_tile, (int)gridDim.x);
+        sat_conv_epilogue16<2>(ta, acc, reinterpret_cast<float (*)[68]>(lds_pool) + wave * 32, red_lds, ep_lds, lane, wave);
     } else
     if (wave_on && so >= 1 && ((t0 << so) - a.out_shift) >= 0 && (((t0 + SAT_T_T - 1) << so) + smask_o - a.out_shift) < p.Tout) {
         // depth-to-space epilogue of an INTERIOR tile (round 6): the four consecutive accumulator rows of a lane are four consecutive TIME steps
@@ -507,16 +400,8 @@ sat_conv1d_bf16x3_kernel(SatConvBfLaunch a) {
 #pragma unroll
                             for (int e = 0; e < GL; ++e) {
                                 const int col = col0 + e;
-                                float v = acc[mi][ni][rg * 4 + gp * GL + e] + ep_lds[0][col];
-                                if (bwd) {
-                                    const SatSnakeGrad g = sat_snake_grad(xv[rg][gp][ni][e], ep_lds[1][col], ep_lds[2][col]);
-                                    pda[e] += v * g.dla;
-                                    pdb[e] += v * g.dlb;
-                                    v *= g.dx;
-                                }
-                                v += rv[rg][gp][ni][e];
-                                if (p.tanh_out) v = tanhf(v);
-                                ov[e] = v;
+                                ov[e] = sat_conv_finish(acc[mi][ni][rg * 4 + gp * GL + e], ep_lds[0][col], bwd, xv[rg][gp][ni][e], ep_lds[1][col], ep_lds[2][col],
+                                                        rv[rg][gp][ni][e], p.tanh_out, pda[e], pdb[e]);
                             }
                             if (m_ok) *reinterpret_cast<vecu*>(p.y + ((size_t)b * p.Cout + co) * p.Tout + ((q << so) + (m & smask_o) - a.out_shift)) = ov;
                         }
@@ -576,15 +461,10 @@ sat_conv1d_bf16x3_kernel(SatConvBfLaunch a) {
                     const int q = t0 + t_w + ni * 32 + l31;
                     const int t = (q << so) + (m & smask_o) - a.out_shift;
                     const bool ok = (okb >> (2 * r + ni)) & 1u;
-                    float v = acc[mi][ni][r] + bias;
-                    if (bwd) {
-                        const SatSnakeGrad g = sat_snake_grad(xv[r][ni], a2, b2);
-                        pda += ok ? v * g.dla : 0.0f;
-                        pdb += ok ? v * g.dlb : 0.0f;
-                        v *= g.dx;
-                    }
-                    v += rv[r][ni];
-                    if (p.tanh_out) v = tanhf(v);
+                    float da = 0.f, db = 0.f;                  // (an element outside the tensor came from a clamped address: its terms are dropped)
+                    const float v = sat_conv_finish(acc[mi][ni][r], bias, bwd, xv[r][ni], a2, b2, rv[r][ni], p.tanh_out, da, db);
+                    pda += ok ? da : 0.0f;
+                    pdb += ok ? db : 0.0f;
                     if (ok) p.y[((size_t)b * p.Cout + co) * p.Tout + t] = v;
                 }
                 if (bwd) {

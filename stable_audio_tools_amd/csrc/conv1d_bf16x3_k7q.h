@@ -15,7 +15,7 @@
 //     Two stages of 76 KiB; the wait for chunk c+1 (vmcnt(0)) sits in front of the middle barrier of chunk c's second phase: the
 //     first read of chunk c+1 is two barriers later for the waiting wave and one barrier after the other wave row's wait; a stage
 //     is overwritten from the phase after the barrier that retired its last reads.
-//   * epilogue: as conv1d_bf16x3_k7.h (bias, dsnake + its per-channel sums, residual, tanh; 16-byte accesses through an LDS
+//   * epilogue: conv_epilogue.h (bias, dsnake + its per-channel sums, residual, tanh, plane emission; 16-byte accesses through an LDS
 //     transposition that reuses the drained stage memory).
 //   * round 6 (VARIANT 3, the shipped K loop): the next chunk's LDS-DMA is issued INSIDE the MFMA sections, not beside the fragment reads
 //     (the item above describes VARIANT 1, kept as the A / B arm: SatConvBfLaunch::dma_in_mfma, ops.k7q_dma_in_mfma) — see INMFMA below.
@@ -95,11 +95,11 @@ typedef uint32_t u32x2_q __attribute__((ext_vector_type(2)));
 template <int VARIANT = 1, bool FUSED = false, bool PERSIST = false>
 __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatConvBfLaunch a) {
     static_assert(!(FUSED && PERSIST), "the fused unit is not persistent");
-    // VARIANT 1 (shipped): the next chunk's LDS-DMA goes out longest latency first — phase 0 issues its activation pieces (HBM) and
+    static_assert(VARIANT == 1 || VARIANT == 3, "the two K loops below");
+    // VARIANT 1: the next chunk's LDS-DMA goes out longest latency first — phase 0 issues its activation pieces (HBM) and
     // taps 0, 1, phase 1 taps 2..6 (L2-resident weights) — with COUNTED waits: phase 1 leaves taps 4-6 in flight (vmcnt(3)), they are
     // retired by the next chunk's phase 0 (which leaves its own new pieces in flight: 5 for waves 0-3, 4 for waves 4-7) one phase
-    // before they are read.  VARIANT 0: weights first, vmcnt(0) once per chunk (3-4 % slower at C = 128 / 256, profiles/EXPERIMENTS.md).
-    constexpr bool REORDER = (VARIANT & 1) != 0;
+    // before they are read.
     // VARIANT 3 (round 6): the next chunk's LDS-DMA is issued INSIDE the MFMA sections — a piece costs 100-185 cycles of issue in a read section that
     // also carries 32 ds_read_b128 and ~60 between MFMAs (MI355X_MICROARCH.md), and an ablation put the DMA at 21-24 % of the launch
     // (profiles/r06_experiments/k7q_ablation/).  Phase 0 issues [activations, taps 0-3] of chunk c+1 after its taps' MFMAs, phase 1 [taps 4-6];
@@ -247,21 +247,14 @@ __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatCon
         for (int u = 0; u < 4; ++u) load_frags(fr[u], sb, u);
         if constexpr (INMFMA) {
             SAT_WAIT_VMCNT(0);                             // taps 4 .. K-1 of THIS chunk (issued in the previous chunk's second MFMA section)
-        } else if constexpr (REORDER) {
-            if (more) {
-                issue_a(c + 1, (c + 1 + SPAR) & 1, 0); issue_a(c + 1, (c + 1 + SPAR) & 1, 1); issue_a(c + 1, (c + 1 + SPAR) & 1, 2);
-                issue_w(c + 1, (c + 1 + SPAR) & 1, 0); issue_w(c + 1, (c + 1 + SPAR) & 1, 1);
-                if (K != SAT_K7Q_TAPS) { SAT_WAIT_VMCNT(0); }
-                else if (wave < 4) { SAT_WAIT_VMCNT(5); }
-                else { SAT_WAIT_VMCNT(4); }
-            } else {
-                SAT_WAIT_VMCNT(0);
-            }
+        } else if (more) {
+            issue_a(c + 1, (c + 1 + SPAR) & 1, 0); issue_a(c + 1, (c + 1 + SPAR) & 1, 1); issue_a(c + 1, (c + 1 + SPAR) & 1, 2);
+            issue_w(c + 1, (c + 1 + SPAR) & 1, 0); issue_w(c + 1, (c + 1 + SPAR) & 1, 1);
+            if (K != SAT_K7Q_TAPS) { SAT_WAIT_VMCNT(0); }
+            else if (wave < 4) { SAT_WAIT_VMCNT(5); }
+            else { SAT_WAIT_VMCNT(4); }
         } else {
-            if (more) {
-#pragma unroll
-                for (int tap = 0; tap < 5; ++tap) issue_w(c + 1, (c + 1 + SPAR) & 1, tap);
-            }
+            SAT_WAIT_VMCNT(0);
         }
         SAT_WAIT_LGKM0();
         SAT_RAW_BARRIER();
@@ -294,16 +287,10 @@ __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatCon
             if (4 + u < K) load_frags(fr[u], sb, 4 + u);
         if constexpr (INMFMA) {
             SAT_WAIT_VMCNT(0);                             // activations and taps 0-3 of chunk c + 1 (issued in this chunk's first MFMA section)
-        } else if constexpr (REORDER) {
-            if (more) {
-#pragma unroll
-                for (int tap = 2; tap < SAT_K7Q_TAPS; ++tap) issue_w(c + 1, (c + 1 + SPAR) & 1, tap);
-                if (K == SAT_K7Q_TAPS) { SAT_WAIT_VMCNT(3); } else { SAT_WAIT_VMCNT(0); }
-            }
         } else if (more) {
-            issue_w(c + 1, (c + 1 + SPAR) & 1, 5); issue_w(c + 1, (c + 1 + SPAR) & 1, 6);
-            issue_a(c + 1, (c + 1 + SPAR) & 1, 0); issue_a(c + 1, (c + 1 + SPAR) & 1, 1); issue_a(c + 1, (c + 1 + SPAR) & 1, 2);
-            SAT_WAIT_VMCNT(0);                             // chunk c+1 has landed (this wave's pieces; the barriers publish the others')
+#pragma unroll
+            for (int tap = 2; tap < SAT_K7Q_TAPS; ++tap) issue_w(c + 1, (c + 1 + SPAR) & 1, tap);
+            if (K == SAT_K7Q_TAPS) { SAT_WAIT_VMCNT(3); } else { SAT_WAIT_VMCNT(0); }
         }
         SAT_WAIT_LGKM0();
         SAT_RAW_BARRIER();
@@ -354,186 +341,16 @@ __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatCon
     // through it cannot be hoisted out of the tile loop, where ~40 scalar registers of epilogue-only arguments would stay live across
     // the K loop (the first build of this variant spilled 112 SGPRs and, through their v_writelane homes, 171 VGPRs)
 #if defined(SAT_HIPEMU)
-    const SatConvBfLaunch& ea = a;
+    const SatConvBfLaunch* eap = &a;
 #else
     typedef const __attribute__((address_space(4))) SatConvBfLaunch* sat_kargs_t;
     sat_kargs_t eap = (sat_kargs_t)__builtin_amdgcn_kernarg_segment_ptr();
     if constexpr (PERSIST) asm volatile("" : "+s"(eap));
-    const auto& ea = *eap;
 #endif
-    const auto& ep = ea.p;
     auto epilogue = [&](float* y_out, const float* res_in, bool emit_on) __attribute__((always_inline)) {
-    const int b = e_b, t_tile = e_t_tile, co0 = e_co0, t0 = e_t0;      // (shadow the DMA lambdas' — PERSIST: already the next tile's)
-    short* em_hi_ = emit_on ? ea.em_hi : nullptr;
-    short* em_lo_ = emit_on ? ea.em_lo : nullptr;
-    // ------------------------------------ epilogue (as the generic kernel) ------------------------------------
-    const bool bwd = (ep.x2 != nullptr);
-    const bool wave_on = (co0 + co_w) < ea.cout_v;
-    const bool mi1_on = (co0 + co_w + 32) < ea.cout_v;
-    if (bwd) {
-        __syncthreads();
-        for (int i = tid; i < 2 * TW * CO_T; i += NT) (&red_lds[0][0][0])[i] = 0.0f;
-        __syncthreads();
-    }
-    const bool vec4 = (ep.Tout & 3) == 0 && (((uintptr_t)y_out | (uintptr_t)ep.x2 | (uintptr_t)res_in) & 15) == 0;
-    if (vec4) {
-        // 16-byte epilogue: each wave transposes its accumulators through LDS (the stage memory is free now) so that
-        // a lane owns 4 consecutive time steps of a row; the x2 / res loads of a 32-row half are all issued before use.
-        if (!bwd) __syncthreads();                          // (bwd already synchronised above)
-        float (*tile)[68] = reinterpret_cast<float (*)[68]>(lds) + wave * 32;       // 32 x 68 floats per wave, in the (drained) stage memory
-        const int lr = lane >> 4, t4 = (lane & 15) * 4;    // this lane's row within a group of 4, its 4 time steps
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-            const bool half_on = wave_on && (mi == 0 || mi1_on);
-            if (mi == 1) __syncthreads();                   // every wave is done reading its first half
-            if (half_on) {
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) tile[(r & 3) + 8 * (r >> 2) + 4 * hi][ni * 32 + l31] = acc[mi][ni][r];
-            }
-            __syncthreads();                                // (a wave only reads its own tile: this orders its own lanes)
-            if (half_on) {
-                const int tg = t0 + t_w + t4;
-                f32x4 xv[8], rv[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int col = co_w + mi * 32 + j * 4 + lr;
-                    const int co = co0 + col;
-                    const bool ok = co < ea.cout_v && tg < ep.Tout;
-                    const size_t o = ((size_t)b * ep.Cout + (ok ? co : 0)) * ep.Tout + (ok ? tg : 0);
-                    xv[j] = (bwd && ok) ? *reinterpret_cast<const f32x4*>(ep.x2 + o) : f32x4{0.f, 0.f, 0.f, 0.f};
-                    rv[j] = (res_in && ok) ? *reinterpret_cast<const f32x4*>(res_in + o) : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int row = j * 4 + lr;
-                    const int col = co_w + mi * 32 + row;
-                    const int co = co0 + col;
-                    const bool ok = co < ea.cout_v && tg < ep.Tout;
-                    const f32x4 av = *reinterpret_cast<const f32x4*>(&tile[row][t4]);
-                    const float bias = ep_lds[0][col];
-                    const float a2 = ep_lds[1][col], b2 = ep_lds[2][col];
-                    float pda = 0.f, pdb = 0.f;
-                    f32x4 ov;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = av[e] + bias;
-                        if (bwd) {
-                            const SatSnakeGrad g = sat_snake_grad(xv[j][e], a2, b2);
-                            pda += v * g.dla;
-                            pdb += v * g.dlb;
-                            v *= g.dx;
-                        }
-                        v += rv[j][e];
-                        if (ep.tanh_out) v = tanhf(v);
-                        ov[e] = v;
-                    }
-                    if (ok) *reinterpret_cast<f32x4*>(y_out + ((size_t)b * ep.Cout + co) * ep.Tout + tg) = ov;
-                    if (em_hi_) {
-                        // plane emission (as conv1d_bf16x3.hip's generic kernel), step 1: the consumer's activation of the finished
-                        // values goes back into this lane's own cell of the transposition tile (rows past Cout hold act(0) = 0)
-                        f32x4 ev = ov;
-                        if (ea.em_a) {
-                            const float ea = ep_lds[3][col], eib = ep_lds[4][col];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) ev[e] = sat_snake(ov[e], ea, eib);
-                        }
-                        if (!ok) ev = f32x4{0.f, 0.f, 0.f, 0.f};
-                        *reinterpret_cast<f32x4*>(&tile[row][t4]) = ev;
-                    }
-                    if (bwd) {
-                        if (!ok) { pda = 0.f; pdb = 0.f; }
-#pragma unroll
-                        for (int m = 8; m >= 1; m >>= 1) {     // sum over the 16 lanes that share this row
-                            pda += __shfl_xor(pda, m);
-                            pdb += __shfl_xor(pdb, m);
-                        }
-                        if ((lane & 15) == 0) {
-                            red_lds[0][wave % TW][col] = pda;
-                            red_lds[1][wave % TW][col] = pdb;
-                        }
-                    }
-                }
-                if (em_hi_) {
-                    // step 2: the tile read COLUMN-wise — 8 consecutive channels of one time step = one 16-byte plane row
-                    sat_wave_sync();
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int c8i = ((co0 + co_w + mi * 32) >> 3) + g;
-                        const int tq = t0 + t_w + lane;
-                        float v8[8];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v8[e] = tile[g * 8 + e][lane];
-                        uint32_t eh[4], el[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) sat_split2_pk(v8[2 * e], v8[2 * e + 1], &eh[e], &el[e]);
-                        if (c8i < ea.em_c8 && tq < ep.Tout) {
-                            const size_t o = (((size_t)b * ea.em_c8 + c8i) * ea.em_rows + SAT_K7P_LEAD + tq) * 8;
-                            *reinterpret_cast<u32x4*>(em_hi_ + o) = u32x4{eh[0], eh[1], eh[2], eh[3]};
-                            *reinterpret_cast<u32x4*>(em_lo_ + o) = u32x4{el[0], el[1], el[2], el[3]};
-                        }
-                    }
-                }
-            }
-        }
-    } else
-    if (wave_on) {
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-            if (mi == 1 && !mi1_on) break;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int col = co_w + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                const int co = co0 + col;
-                const bool co_ok = co < ea.cout_v;
-                const float bias = ep_lds[0][col];
-                const float a2 = ep_lds[1][col], b2 = ep_lds[2][col];
-                float pda = 0.f, pdb = 0.f;
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    const int t = t0 + t_w + ni * 32 + l31;
-                    if (co_ok && t < ep.Tout) {
-                        const size_t o = ((size_t)b * ep.Cout + co) * ep.Tout + t;
-                        float v = acc[mi][ni][r] + bias;
-                        if (bwd) {
-                            const SatSnakeGrad g = sat_snake_grad(ep.x2[o], a2, b2);
-                            pda += v * g.dla;
-                            pdb += v * g.dlb;
-                            v *= g.dx;
-                        }
-                        if (res_in) v += res_in[o];
-                        if (ep.tanh_out) v = tanhf(v);
-                        y_out[o] = v;
-                    }
-                }
-                if (bwd) {
-                    pda = sat_half_sum(pda);
-                    pdb = sat_half_sum(pdb);
-                    if (l31 == 0) {
-                        red_lds[0][wave % TW][col] = pda;
-                        red_lds[1][wave % TW][col] = pdb;
-                    }
-                }
-            }
-        }
-    }
-    if (bwd) {
-        __syncthreads();
-        const int m = co0 + tid;
-        if (tid < CO_T && m < ea.cout_v) {
-            float sa = 0.f, sb = 0.f;
-#pragma unroll
-            for (int w = 0; w < TW; ++w) {
-                sa += red_lds[0][w][tid];
-                sb += red_lds[1][w][tid];
-            }
-            const size_t row = (size_t)b * t_tiles + t_tile;
-            const size_t nrows_p = (size_t)ep.B * t_tiles;
-            ep.part_da[(size_t)m * nrows_p + row] = sa;
-            ep.part_db[(size_t)m * nrows_p + row] = sb;
-        }
-    }
+        // (the tile's own coordinates, not the DMA lambdas' — PERSIST: already the next tile's); 32 x 68 floats per wave in the (drained) stage memory
+        const SatConvEpArgs ta = sat_conv_ep_args(eap, y_out, res_in, emit_on, e_b, e_co0, e_t0, e_t_tile, t_tiles);
+        sat_conv_epilogue_plain<TW, NT>(ta, acc, reinterpret_cast<float (*)[68]>(lds) + wave * 32, red_lds, ep_lds, tid, lane, wave);
     };
 
     if constexpr (FUSED) {

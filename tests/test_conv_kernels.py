@@ -220,6 +220,59 @@ def test_edge_conv_emission_gpu(hip):
     _edge_emit_case(hip, "cuda")
 
 
+def _generic_emit_case(ops, dev):
+    """Plane emission of the generic bf16x3 kernel's 16-byte epilogue (a k = 1 conv writes the planes of the k7 conv that reads it next): the
+    three ways the model runs it — emit=(la, lb) and emit=True forward, emit=True with the dsnake data-gradient (dh's planes).  T = 132: two time
+    tiles, the second with 4 valid steps; Cout = 20: a partial group of 8 in the first 32-row half, Cout = 40: a partial second half, Cout = 128: the
+    first time tile lies inside the tensor and takes the epilogue's unchecked loads.  hi + lo of the planes == act(returned y) to 2^-15, rows
+    around the sequence and channels past Cout zero; y / d log-alpha / d log-beta against float64."""
+    B, Cin, T = 2, 24, 132
+    for Cout in (20, 40, 128):
+        gen = torch.Generator().manual_seed(13 + Cout)
+        x = torch.randn(B, Cin, T, generator=gen).to(dev)
+        w = (torch.randn(Cout, Cin, 1, generator=gen) * .2).to(dev)
+        bias = torch.randn(Cout, generator=gen).to(dev)
+        lai, lbi = (torch.randn(Cin, generator=gen) * .3).to(dev), (torch.randn(Cin, generator=gen) * .3).to(dev)
+        la, lb = (torch.randn(Cout, generator=gen) * .3).to(dev), (torch.randn(Cout, generator=gen) * .3).to(dev)
+        x2 = torch.randn(B, Cout, T, generator=gen).to(dev)
+        a2, b2 = (torch.randn(Cout, generator=gen) * .3).to(dev), (torch.randn(Cout, generator=gen) * .3).to(dev)
+        wp = ops.pack_bf16x3(w, 0, 1)
+        x64, w64, bias64 = x.double().cpu(), w.double().cpu(), bias.double().cpu()
+        fwd = F.conv1d(snake(x64, lai.double().cpu(), lbi.double().cpu()), w64, bias64)
+        g = F.conv1d(x64, w64, bias64)
+        d64 = [t.double().cpu().requires_grad_(True) for t in (x2, a2, b2)]
+        dsn = torch.autograd.grad(snake(*d64), d64, g)              # g * dsnake(x2), sum g * d snake / d log-alpha2, ... / d log-beta2
+        c8 = (Cout + 7) // 8
+        for esnake, dsnake, refs in (((la, lb), None, [fwd]), (None, None, [fwd]), (None, (x2, a2, b2), dsn)):
+            emit = esnake if esnake is not None else True
+            if dsnake is None:
+                outs = [ops.conv1d_bf16x3(x, wp, Cout, 1, bias=bias, snake=(lai, lbi), emit=emit)]
+            else:
+                outs = list(ops.conv1d_bf16x3(x, wp, Cout, 1, bias=bias, dsnake=dsnake, emit=emit))
+            for a, b in zip(outs, refs):
+                err = (a.double().cpu() - b).abs().max().item()
+                assert err <= TOL * max(b.abs().max().item(), FLOOR[0]), (Cout, err, b.abs().max().item())
+            y = outs[0]
+            em = ops._take_emitted(y, esnake)
+            assert em is not None
+            rows = em["rows"]
+            hi = em["hi"].view(torch.bfloat16).float().view(B, c8, rows, 8).cpu()
+            lo = em["lo"].view(torch.bfloat16).float().view(B, c8, rows, 8).cpu()
+            got = (hi + lo).permute(0, 1, 3, 2).reshape(B, c8 * 8, rows)        # (B, channel, plane row)
+            want = snake(y.cpu(), la.cpu(), lb.cpu()) if esnake is not None else y.cpu()
+            assert (got[:, :Cout, 32:32 + T] - want).abs().max() <= 2.0 ** -15 * want.abs().max()
+            assert got[:, Cout:, :].abs().sum() == 0 and got[:, :, :32].abs().sum() == 0 and got[:, :, 32 + T:].abs().sum() == 0      # (Cout = 40, 128: no channel past Cout)
+
+
+def test_generic_conv_emission_sim(emu):
+    _generic_emit_case(emu, "cpu")
+
+
+@pytest.mark.gpu
+def test_generic_conv_emission_gpu(hip):
+    _generic_emit_case(hip, "cuda")
+
+
 @pytest.mark.parametrize("case", EDGE_CASES)
 def test_edge_conv_sim(emu, case):
     _run_edge(emu, "cpu", case, True)
