@@ -581,6 +581,27 @@ int sat_cast_bf16_dual(const void* src, long long lds, void* dst, long long ldd,
  * A' · B'^T = hi·hi + hi·lo + lo·hi  (|x - hi - lo| <= 2^-17 |x|). */
 int sat_split_bf16x3(const float* src, long long lds, void* dst, long long ldd, int R, int C, int side, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * DiT optimisation step, front and tail (csrc/diffusion_step.hip) — DiffusionCondTrainingWrapper.training_step,
+ * training/diffusion.py:377-379, :406-420 (noising, targets) and MSELoss with a padding mask, training/losses/losses.py:76-89.
+ * Replaces the torch elementwise chain, `mse_loss[mask].mean()` (a host sync) and their autograd.  No atomics: bit-reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+/* x, noise, noised, targets: (B, C, T) fp32 contiguous; t: (B) fp32 on the device.  xs = x * inv_scale (1 / pretransform scale).
+ * objective 0 ("v"): alpha = cos(t pi/2), sigma = sin(t pi/2), noised = xs*alpha + noise*sigma, targets = noise*alpha - xs*sigma;
+ * objective 1 ("rectified_flow" / "rf_denoiser"): alpha = 1 - t, sigma = t, targets = noise - xs.  B <= 65535. */
+int sat_diffusion_noise(const float* x, const float* noise, const float* t, float* noised, float* targets, int B, int C, int T,
+                        int objective, float inv_scale, void* stream);
+/* res[0] = sum over selected (b, c, t) of (out - targets)^2 / count, res[1] = count = C * sum(mask) (B*C*T when mask == NULL; counted
+ * in integers, stored as a float).  out: (B, C, T) fp32 (dtype 0) | bf16 (dtype 1); targets fp32; mask: (B, T) bytes, non-zero = selected.
+ * Masked elements are skipped, not multiplied by zero; an empty selection gives NaN.  work: 2 * sat_masked_mse_nblocks(B, C, T) 4-byte
+ * words of partials (two launches, the second sums them in index order). */
+int sat_masked_mse_nblocks(int B, int C, int T);
+int sat_masked_mse_fwd(const void* out, const float* targets, const unsigned char* mask, float* work, float* res, int B, int C, int T,
+                       int dtype, void* stream);
+/* dout = mask ? 2 * (out - targets) * gloss[0] / res[1] : 0, in out's dtype; res = the forward's result, gloss: device scalar. */
+int sat_masked_mse_bwd(const void* out, const float* targets, const unsigned char* mask, const float* res, const float* gloss,
+                       void* dout, int B, int C, int T, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

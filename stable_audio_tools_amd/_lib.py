@@ -146,6 +146,11 @@ SIGNATURES = {
     "sat_sampler_step": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _I, _P]),
     "sat_sampler_step_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _I, _P]),
     "sat_gate_residual_bwd": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _P]),
+    # diffusion_step.hip
+    "sat_diffusion_noise": (_I, [_P] * 5 + [_I] * 4 + [_F, _P]),
+    "sat_masked_mse_nblocks": (_I, [_I, _I, _I]),
+    "sat_masked_mse_fwd": (_I, [_P] * 5 + [_I] * 4 + [_P]),
+    "sat_masked_mse_bwd": (_I, [_P] * 6 + [_I] * 4 + [_P]),
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libsat_amd.so")

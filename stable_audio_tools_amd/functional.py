@@ -50,6 +50,32 @@ def mean_all(x, ops=None):
     return SumAllFn.apply(x, ops) / x.numel()
 
 
+class MaskedMSEFn(torch.autograd.Function):
+    """MSELoss("output", "targets", mask_key="padding_mask") of the diffusion wrapper (training/losses/losses.py:76-89, used at
+    training/diffusion.py:270-277): the mean of (out - targets)^2 over the elements a (B, T) padding mask selects (every element without
+    one), on ops.masked_mse / masked_mse_bwd.  The reference's `mse_loss[mask].mean()` synchronises with the host; this node never does,
+    and its reduction is not one of torch's multi-block ones (ops.sum_all).  out (B, C, T) fp32 | bf16 -> 0-d fp32 loss."""
+
+    @staticmethod
+    def forward(ctx, out, targets, mask=None, ops=None):
+        o = _ops(ops)
+        out_c = out.detach().contiguous()
+        res = o.masked_mse(out_c, targets, mask)
+        ctx.save_for_backward(out_c, targets, mask, res)
+        ctx.ops = o
+        return res[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        out, targets, mask, res = ctx.saved_tensors
+        gloss = g.detach().to(torch.float32).contiguous().view(())
+        return ctx.ops.masked_mse_bwd(out, targets, mask, res, gloss), None, None, None
+
+
+def masked_mse(out, targets, mask=None, ops=None):
+    return MaskedMSEFn.apply(out, targets, mask, ops)
+
+
 class DerivedCache:
     """Derived copies of one conv layer's parameters (folded weight, packed bf16x3 planes, SnakeBeta constants) for the passes in
     which nothing is trained: each entry is valid for one (storage, torch version counter, invalidation epoch) of its sources

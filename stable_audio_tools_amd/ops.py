@@ -1633,6 +1633,60 @@ class SatOps:
         self._chk(self.lib.sat_split_bf16x3(_ptr(src), src.stride(0), _ptr(dst), 3 * c, r, c, side, self._stream(src)))
         return dst
 
+    # ------------------------------------------------------------------ DiT train step: noising, masked loss (csrc/diffusion_step.hip)
+    # training.DiTTrainStep forms noised inputs / targets and the (padding-masked) MSE on these kernels.  False: the torch formulation of
+    # the same maths, torch.where + functional.sum_all for the masked mean (A/B: bench.py --ops-set dit_step_fused=0)
+    dit_step_fused = True
+    OBJECTIVES = {"v": 0, "rectified_flow": 1, "rf_denoiser": 1}
+
+    def diffusion_noise(self, x, noise, t, objective, latent_scale=1.0):
+        """(noised, targets) of training/diffusion.py:377-379, :406-420 for x, noise (B, C, T) fp32 and device timesteps t (B,):
+        x / latent_scale first; "v": alpha, sigma = cos, sin(t pi/2), targets = noise*alpha - x*sigma; "rectified_flow" / "rf_denoiser":
+        alpha, sigma = 1 - t, t, targets = noise - x; noised = x*alpha + noise*sigma."""
+        if objective not in self.OBJECTIVES:
+            raise ValueError(f"diffusion_noise: unknown objective {objective!r}")
+        self._f32(x, noise, t)
+        if x.dim() != 3 or noise.shape != x.shape or tuple(t.shape) != (x.shape[0],):
+            raise ValueError("diffusion_noise: x, noise (B, C, T) and t (B,)")
+        b, c, tt = x.shape
+        noised, targets = torch.empty_like(x), torch.empty_like(x)
+        self._chk(self.lib.sat_diffusion_noise(_ptr(x), _ptr(noise), _ptr(t), _ptr(noised), _ptr(targets), b, c, tt, self.OBJECTIVES[objective],
+                                               1.0 / float(latent_scale), self._stream(x)))
+        return noised, targets
+
+    def _mse_args(self, who, out, targets, mask):
+        dt = self._dt(out)
+        self._f32(targets)
+        if out.dim() != 3 or targets.shape != out.shape or not out.is_contiguous():
+            raise ValueError(f"{who}: out, targets contiguous (B, C, T)")
+        b, c, t = out.shape
+        if mask is not None:
+            if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (b, t) or not mask.is_contiguous() or mask.device != out.device:
+                raise ValueError(f"{who}: mask must be a contiguous (B, T) bool / uint8 tensor on out's device")
+        return dt, b, c, t
+
+    def masked_mse(self, out, targets, mask=None):
+        """MSELoss with a padding mask (training/losses/losses.py:76-89) without its host sync: a 2-element fp32 device tensor
+        (loss, count) with loss = sum over selected (b, c, t) of (out - targets)^2 / count, count = C * mask.sum() (B*C*T without a mask).
+        out (B, C, T) fp32 | bf16, targets fp32, mask (B, T) bool.  Masked elements are skipped; nothing selected gives NaN."""
+        dt, b, c, t = self._mse_args("masked_mse", out, targets, mask)
+        nb = self.lib.sat_masked_mse_nblocks(b, c, t)
+        work = torch.empty(2 * nb, dtype=torch.float32, device=out.device)
+        res = torch.empty(2, dtype=torch.float32, device=out.device)
+        self._chk(self.lib.sat_masked_mse_fwd(_ptr(out), _ptr(targets), _ptr(mask), _ptr(work), _ptr(res), b, c, t, dt, self._stream(out)))
+        return res
+
+    def masked_mse_bwd(self, out, targets, mask, res, gloss):
+        """dout = mask ? 2 (out - targets) gloss / count : 0 in out's dtype; res: masked_mse's result, gloss: 0-d fp32 device tensor."""
+        dt, b, c, t = self._mse_args("masked_mse_bwd", out, targets, mask)
+        self._f32(res, gloss)
+        if res.numel() != 2 or gloss.numel() != 1:
+            raise ValueError("masked_mse_bwd: res holds (loss, count), gloss one value")
+        dout = torch.empty_like(out)
+        self._chk(self.lib.sat_masked_mse_bwd(_ptr(out), _ptr(targets), _ptr(mask), _ptr(res), _ptr(gloss), _ptr(dout), b, c, t, dt,
+                                              self._stream(out)))
+        return dout
+
     # ------------------------------------------------------------------ optimizer
     def adamw_step_dev(self, p, g, m, v, hyper, beta1, beta2, eps, weight_decay, ema=None):
         """adamw_step with (lr, 1 - beta1^t, sqrt(1 - beta2^t), grad_scale, ema_decay) read from the device tensor `hyper` (5 fp32)."""

@@ -4,6 +4,8 @@ of x folded into the guidance kernel.
 Same names, arguments and results as the reference functions:
 
     DistributionShift          :24-41     time-shift of the schedule by sequence length
+    sample_timesteps_logsnr    :43-66     training timesteps from a Gaussian over logSNR
+    truncated_logistic_normal_rescaled :67-95   training timesteps from a left-truncated logit-normal, rescaled to [0, 1)
     sample_discrete_euler      :98-135    rectified-flow Euler
     sample_rk4                 :138-177   4th-order Runge-Kutta (4 model evaluations per step)
     sample_flow_dpmpp          :179-219   DPM-Solver++(2M) for rectified-flow models
@@ -48,6 +50,25 @@ class DistributionShift:
         if self.use_sine:
             t_out = torch.sin(t_out * math.pi / 2)
         return t_out
+
+
+def sample_timesteps_logsnr(batch_size, mean_logsnr=-1.2, std_logsnr=2.0, z=None):
+    """inference/sampling.py:43-66, on the CPU: logSNR ~ N(mean, std^2), t = sigmoid(-logSNR) (logSNR = ln((1 - t) / t)), clamped to
+    [1e-4, 1 - 1e-4].  z (extension): the standard-normal draw, (batch_size,); None draws torch.randn(batch_size) as the reference does."""
+    z = torch.randn(batch_size) if z is None else z
+    return torch.sigmoid(-(z * std_logsnr + mean_logsnr)).clamp(1e-4, 1 - 1e-4)
+
+
+def truncated_logistic_normal_rescaled(shape, left_trunc=0.075, right_trunc=1, z=None):
+    """inference/sampling.py:67-95, on the CPU: a logit-normal sample whose lowest `left_trunc` of the VALUE range [0, 1] is cut away —
+    the normal draw's CDF value is squeezed into [Phi(logit(left_trunc)), Phi(logit(right_trunc))], mapped back through the inverse CDF and
+    the sigmoid — then stretched so that left_trunc lands on 0.  z (extension): the standard-normal draw of `shape`; None: torch.randn."""
+    z = torch.randn(shape) if z is None else z
+    normal = torch.distributions.Normal(0, 1)
+    lo = normal.cdf(torch.logit(torch.tensor(left_trunc)))
+    hi = normal.cdf(torch.logit(torch.tensor(right_trunc)))
+    squeezed = lo + (hi - lo) * normal.cdf(z)
+    return (torch.sigmoid(normal.icdf(squeezed)) - left_trunc) / (right_trunc - left_trunc)
 
 
 def get_alphas_sigmas(t):

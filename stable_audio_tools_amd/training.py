@@ -852,17 +852,29 @@ class GraphedTrainStep:
 class DiTTrainStep:
     """One optimisation step of the conditioned DiT on (pre-encoded) latents, data-parallel over the default
     process group — restated from DiffusionCondTrainingWrapper.training_step
-    (training/diffusion.py:332-487): t ~ Sobol-uniform (:381-383, self.rng = SobolEngine(1, scramble=True) :253) or
-    logit-normal (:384-385); alphas/sigmas (:406-409); noised = x*alpha + noise*sigma (:415); v / rectified-flow
-    targets (:417-420); model(noised, t, cross_attn_cond, global_embed, cfg_dropout_prob) (:440 -> DiTWrapper.forward
-    models/diffusion.py:520-557); MSE (:449, losses.py:66-91); EMA (:489-491); AdamW.  The conditioner (T5 etc.) is out of
-    scope: its output tensors are inputs here.  mixed precision: `autocast_dtype=torch.bfloat16` runs the projections and
-    the HIP kernels in bf16 with fp32 master weights (Lightning '--precision bf16-mixed')."""
+    (training/diffusion.py:332-487): padding-mask dropout (:353) and resize (:375); latents / pretransform scale (:377-379);
+    t ~ Sobol-uniform (:381-383, self.rng = SobolEngine(1, scramble=True) :253), logit-normal (:384-385), truncated logit-normal, flipped
+    (:386-391) or log-SNR Gaussian (:392-393); distribution shift by sequence length (:397-399); p_one_shot (:401-403);
+    alphas/sigmas (:406-409); noised = x*alpha + noise*sigma (:415); v / rectified-flow targets (:417-420);
+    model(noised, t, cross_attn_cond, global_embed, prepend_cond, cfg_dropout_prob, mask) (:424-440 -> DiTWrapper.forward
+    models/diffusion.py:520-557); MSE over the elements the padding mask selects (:449, losses.py:66-91); EMA (:489-491); AdamW with
+    the InverseLR schedule (:318-330); validation_step's per-timestep losses (:533-564) as validation_losses().  The conditioner (T5
+    etc.) is out of scope: its output tensors are inputs here.  mixed precision: `autocast_dtype=torch.bfloat16` runs the projections
+    and the HIP kernels in bf16 with fp32 master weights (Lightning '--precision bf16-mixed').
+
+    The step never synchronises with the host (the reference's `mse_loss[mask].mean()` does) and reduces nothing to a scalar through
+    torch's multi-block reductions (ops.sum_all): noising / targets and the masked loss run on csrc/diffusion_step.hip
+    (ops.diffusion_noise, functional.MaskedMSEFn); `ops.dit_step_fused = False` is the torch formulation of the same maths (A/B).
+    Not restated: inpainting_config, input_concat_cond (the oracle has no leg for them), log_loss_info."""
 
     def __init__(self, model, lr=5e-5, betas=(0.9, 0.999), weight_decay=1e-3, cfg_dropout_prob=0.1, timestep_sampler="uniform",
                  use_ema=True, autocast_dtype=None, ops=None, ddp_mode="all_reduce", bucket_bytes=256 << 20, seed=0, ddp_overlap=True,
-                 ddp_comm_dtype=None, ddp_single_rank=None):
+                 ddp_comm_dtype=None, ddp_single_rank=None, timestep_sampler_options=None, dist_shift=None, p_one_shot=0.0,
+                 mask_padding=False, mask_padding_dropout=0.0, latent_scale=1.0, lr_scheduler=None,
+                 validation_timesteps=(0.1, 0.3, 0.5, 0.7, 0.9)):
         import math
+        if lr_scheduler is not None and lr_scheduler["type"] != "InverseLR":
+            raise NotImplementedError("only the InverseLR scheduler is restated")
         self._math = math
         self.model = model
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -872,45 +884,136 @@ class DiTTrainStep:
                                   single_rank_exchange=ddp_single_rank, ops=ops)
         self.cfg_dropout_prob = cfg_dropout_prob
         self.timestep_sampler = timestep_sampler
+        self.timestep_sampler_options = dict(timestep_sampler_options or {})
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         self.rng = torch.quasirandom.SobolEngine(1, scramble=True, seed=seed + rank)   # per-rank stream, as train.py:30-33 offsets the seed
         self.autocast_dtype = autocast_dtype
         self.objective = model.diffusion_objective
+        if isinstance(dist_shift, dict):
+            from .sampling import DistributionShift
+            dist_shift = DistributionShift(**dist_shift)
+        self.dist_shift = dist_shift
+        self.p_one_shot = p_one_shot
+        self.mask_padding, self.mask_padding_dropout = mask_padding, mask_padding_dropout
+        self.latent_scale = float(latent_scale)
+        self.base_lr, self.sched = lr, lr_scheduler
+        self.validation_timesteps = tuple(validation_timesteps)
         self.global_step = 0
 
-    def draw_timesteps(self, n, device):
-        if self.timestep_sampler == "uniform":
-            return self.rng.draw(n)[:, 0].to(device)
-        if self.timestep_sampler == "logit_normal":
-            return torch.sigmoid(torch.randn(n, device=device))
-        raise NotImplementedError(f"timestep_sampler {self.timestep_sampler!r} is not restated")
+    def current_lr(self):
+        if self.sched is None:
+            return self.base_lr
+        return inverse_lr(self.global_step, self.base_lr, **self.sched.get("config", {}))      # interval "step" (:324-327)
 
-    def __call__(self, latents, cross_attn_cond=None, global_embed=None, t=None, noise=None):
+    def draw_timesteps(self, n, device, seq_len=None):
+        """:381-403 in order: the sampler, the distribution shift for `seq_len` latent steps, p_one_shot."""
+        if self.timestep_sampler == "uniform":
+            t = self.rng.draw(n)[:, 0].to(device)
+        elif self.timestep_sampler == "logit_normal":
+            t = torch.sigmoid(torch.randn(n, device=device))
+        elif self.timestep_sampler == "trunc_logit_normal":
+            from .sampling import truncated_logistic_normal_rescaled
+            t = 1 - truncated_logistic_normal_rescaled(n).to(device)                # drawn on the CPU and flipped (:388-391)
+        elif self.timestep_sampler == "log_snr":
+            from .sampling import sample_timesteps_logsnr
+            o = self.timestep_sampler_options
+            t = sample_timesteps_logsnr(n, mean_logsnr=o.get("mean_logsnr", -1.2), std_logsnr=o.get("std_logsnr", 2.0)).to(device)
+        else:
+            raise NotImplementedError(f"timestep_sampler {self.timestep_sampler!r} is not restated")
+        if self.dist_shift is not None:
+            if seq_len is None:
+                raise ValueError("draw_timesteps: dist_shift needs the sequence length")
+            t = self.dist_shift.time_shift(t, seq_len)
+        if self.p_one_shot > 0:
+            t = torch.where(torch.rand_like(t) < self.p_one_shot, torch.ones_like(t), t)
+        return t
+
+    def _ops(self):
+        return _fn._ops(self.opt._ops)
+
+    def _noise_targets(self, latents, noise, t):
+        """(noised, targets) of :377-379, :406-420."""
+        ops = self._ops()
+        if ops.dit_step_fused:
+            return ops.diffusion_noise(latents.float().contiguous(), noise.float().contiguous(), t.float().contiguous(), self.objective,
+                                       self.latent_scale)
         math = self._math
-        self.flat.zero_grad()
-        if t is None:
-            t = self.draw_timesteps(latents.shape[0], latents.device)
+        if self.latent_scale != 1.0:
+            latents = latents / self.latent_scale
         if self.objective == "v":
             alphas, sigmas = torch.cos(t * math.pi / 2), torch.sin(t * math.pi / 2)
         else:
             alphas, sigmas = 1 - t, t
         alphas, sigmas = alphas[:, None, None], sigmas[:, None, None]
-        if noise is None:
-            noise = torch.randn_like(latents)
         noised = latents * alphas + noise * sigmas
         targets = noise * alphas - latents * sigmas if self.objective == "v" else noise - latents
-        kw = dict(cross_attn_cond=cross_attn_cond, global_embed=global_embed, cfg_dropout_prob=self.cfg_dropout_prob)
+        return noised, targets
+
+    def _loss(self, out, targets, mask):
+        """MSELoss(mask_key="padding_mask") (losses.py:76-89): the mean over the elements `mask` (B, T) selects, or over all of them."""
+        ops = self._ops()
+        if ops.dit_step_fused:
+            return _fn.masked_mse(out, targets.float(), mask, ops)
+        diff = out.float() - targets.float()
+        if mask is None:
+            return _fn.mean_all(diff * diff, ops)
+        # no boolean indexing (a host sync): masked differences become exact zeros — and get exact zero gradients — through torch.where
+        diff = torch.where(mask[:, None, :], diff, torch.zeros_like(diff))
+        count = _fn.sum_all(mask.to(torch.float32), ops) * diff.shape[1]
+        return _fn.sum_all(diff * diff, ops) / count
+
+    def _padding_mask(self, padding_mask, use_padding_mask, length):
+        """The (B, length) bool mask of this step, or None: :353 (dropout; `use_padding_mask` replaces the draw) and :375 (resize)."""
+        if not self.mask_padding:
+            return None
+        import random
+        use = random.random() > self.mask_padding_dropout if use_padding_mask is None else bool(use_padding_mask)
+        if not use:
+            return None
+        if padding_mask is None:
+            raise ValueError("mask_padding is set: the step needs padding_mask (B, T)")
+        if padding_mask.shape[-1] != length:
+            padding_mask = torch.nn.functional.interpolate(padding_mask.unsqueeze(1).float(), size=length, mode="nearest").squeeze(1)
+        return padding_mask.bool().contiguous()
+
+    def _model(self, noised, t, **kw):
+        kw = {k: v for k, v in kw.items() if v is not None}
         if self.autocast_dtype is not None:
-            with torch.autocast("cuda" if latents.is_cuda else "cpu", dtype=self.autocast_dtype):
-                out = self.model(noised, t, **kw)
-        else:
-            out = self.model(noised, t, **kw)
-        loss = torch.nn.functional.mse_loss(out.float(), targets.float())
+            with torch.autocast("cuda" if noised.is_cuda else "cpu", dtype=self.autocast_dtype):
+                return self.model(noised, t, **kw)
+        return self.model(noised, t, **kw)
+
+    def __call__(self, latents, cross_attn_cond=None, global_embed=None, t=None, noise=None, prepend_cond=None, padding_mask=None,
+                 use_padding_mask=None):
+        self.flat.zero_grad()
+        mask = self._padding_mask(padding_mask, use_padding_mask, latents.shape[2])
+        if t is None:
+            t = self.draw_timesteps(latents.shape[0], latents.device, latents.shape[2])
+        if noise is None:
+            noise = torch.randn_like(latents)
+        noised, targets = self._noise_targets(latents, noise, t)
+        out = self._model(noised, t, cross_attn_cond=cross_attn_cond, global_embed=global_embed, prepend_cond=prepend_cond,
+                          cfg_dropout_prob=self.cfg_dropout_prob, mask=mask)
+        loss = self._loss(out, targets, mask)
         self.comm.mark_backward_start()
         loss.backward()
         self.comm.mark_backward_end()
         self.flat.gather_grads(self.opt._ops)
         self.comm()
-        self.opt.step(grad_scale=self.comm.grad_scale)
+        self.opt.step(lr=self.current_lr(), grad_scale=self.comm.grad_scale)
         self.global_step += 1
         return {"loss": loss.detach()}
+
+    @torch.no_grad()
+    def validation_losses(self, latents, cross_attn_cond=None, global_embed=None, prepend_cond=None, noise=None):
+        """validation_step (:533-564): for every entry of validation_timesteps the UNMASKED loss of the whole batch at that timestep, with
+        fresh noise (or `noise`, one tensor for all timesteps) and cfg_dropout_prob = 0 — {"val/loss_0.1": 0-d tensor, ...}.  Parameters,
+        gradients and optimizer state are left alone."""
+        losses = {}
+        for vt in self.validation_timesteps:
+            t = torch.full((latents.shape[0],), vt, device=latents.device)
+            noised, targets = self._noise_targets(latents, torch.randn_like(latents) if noise is None else noise, t)
+            out = self._model(noised, t, cross_attn_cond=cross_attn_cond, global_embed=global_embed, prepend_cond=prepend_cond,
+                              cfg_dropout_prob=0.0)
+            losses[f"val/loss_{vt:.1f}"] = self._loss(out, targets, None)
+        return losses
