@@ -1256,8 +1256,25 @@ class SatOps:
         return (sums[0:64] if hq > 0 else None, sums[64:128] if hq > 0 else None,
                 sums[128:192] if hq < nh else None, sums[192:256] if hq < nh else None)
 
+    @staticmethod
+    def _swiglu_layout(xin, dout=None):
+        """The SwiGLU kernels index raw pointers: xin a contiguous (..., 2F), dout a contiguous (..., F) of the same rows."""
+        if xin.dim() < 1 or xin.shape[-1] % 2 != 0 or not xin.is_contiguous():
+            raise ValueError("swiglu: xin must be a contiguous (..., 2F) tensor")
+        if dout is not None and (not dout.is_contiguous() or tuple(dout.shape) != (*xin.shape[:-1], xin.shape[-1] // 2)):
+            raise ValueError("swiglu_bwd: dout must be a contiguous (..., F) tensor matching xin")
+
+    @staticmethod
+    def _gate_layout(who, gate, x, *like_x):
+        """The gate / residual kernels index raw pointers: (B, N, D) contiguous tensors and a (B, D) gate view with a unit last stride."""
+        if x.dim() != 3 or not x.is_contiguous() or any(t.shape != x.shape or not t.is_contiguous() for t in like_x):
+            raise ValueError(f"{who}: contiguous (B, N, D) tensors of one shape expected")
+        if gate.dim() != 2 or tuple(gate.shape) != (x.shape[0], x.shape[2]) or (gate.shape[1] > 1 and gate.stride(1) != 1):
+            raise ValueError(f"{who}: gate must be a (B, D) view with a contiguous last dim")
+
     def swiglu(self, xin):
         dt = self._dt(xin)
+        self._swiglu_layout(xin)
         f = xin.shape[-1] // 2
         rows = xin.numel() // (2 * f)
         out = torch.empty(*xin.shape[:-1], f, dtype=xin.dtype, device=xin.device)
@@ -1266,6 +1283,7 @@ class SatOps:
 
     def swiglu_bwd(self, xin, dout):
         dt = self._dt(xin, dout)
+        self._swiglu_layout(xin, dout)
         f = xin.shape[-1] // 2
         rows = xin.numel() // (2 * f)
         dxin = torch.empty_like(xin)
@@ -1275,6 +1293,7 @@ class SatOps:
     def gate_residual(self, x, gate, res):
         """x * sigmoid(1 - gate[b]) + res;  x, res: (B, N, D) contiguous; gate: (B, D) view."""
         dt = self._dt(x, gate, res)
+        self._gate_layout("gate_residual", gate, x, res)
         b, n, d = x.shape
         y = torch.empty_like(x)
         self._chk(self.lib.sat_gate_residual(_ptr(x), _ptr(gate), gate.stride(0), _ptr(res), _ptr(y), b, n, d, dt,
@@ -1284,6 +1303,7 @@ class SatOps:
     def gate_residual_bwd(self, dy, x, gate):
         """Returns dx (B, N, D) and dgate (B, D) fp32 for y = x * sigmoid(1 - gate[b]) + res (d_res = dy)."""
         dt = self._dt(dy, x, gate)
+        self._gate_layout("gate_residual_bwd", gate, x, dy)
         b, n, d = x.shape
         dx = torch.empty_like(x)
         nch = self.lib.sat_gate_residual_bwd_nchunks(n)

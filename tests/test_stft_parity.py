@@ -85,6 +85,45 @@ def test_fir_and_adjoint_simulator(emu):
     assert abs(lhs - rhs) <= 1e-4 * abs(lhs)
 
 
+FIR_TAPS = ["1", "3", "101", "257", "aweighting"]
+FIR_LENGTHS = [1, 5, 1023, 1024, 1025, 2500]          # around the kernel's 1024-sample tile, and shorter than the taps
+
+
+def _fir_case(ops, device, kind):
+    """sat_fir and its adjoint against float64 F.conv1d (cross-correlation, zero pad ntaps // 2; the adjoint: the flipped taps), bounds of
+    tests/fp64_bounds.py with S = the largest |reference|."""
+    import torch.nn.functional as F
+    from fp64_bounds import check, smax
+    gen = torch.Generator().manual_seed(90 + FIR_TAPS.index(kind))
+    taps = stft_oracle.aweighting_fir_taps(SR) if kind == "aweighting" else torch.randn(int(kind), generator=gen)
+    assert taps.dtype == torch.float32 and taps.numel() % 2 == 1
+
+    def formula(x, adjoint):
+        k = (taps.flip(0) if adjoint else taps).to(x.dtype)
+        return F.conv1d(x[:, None, :], k[None, None, :], padding=taps.numel() // 2)[:, 0]
+    for t in FIR_LENGTHS:
+        x = torch.randn(2, t, generator=gen)
+        for adjoint in (False, True):
+            y = ops.fir(x.to(device), taps.to(device), adjoint=adjoint)
+            ref = formula(x.double(), adjoint)
+            check(f"fir[{kind} taps, T={t}{', adjoint' if adjoint else ''}]", y, ref, formula(x, adjoint), smax(ref.abs()))
+    x = torch.randn(2, 64).to(device)
+    for bad in (2, 100, 259):
+        with pytest.raises(RuntimeError, match="ntaps must be odd"):
+            ops.fir(x, torch.randn(bad).to(device))
+
+
+@pytest.mark.parametrize("kind", FIR_TAPS)
+def test_fir_against_float64_sim(emu, kind):
+    _fir_case(emu, "cpu", kind)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", FIR_TAPS)
+def test_fir_against_float64_gpu(hip, kind):
+    _fir_case(hip, "cuda", kind)
+
+
 def test_stft_loss_values_simulator(emu_modules):
     _values("cpu")
 

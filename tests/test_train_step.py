@@ -550,8 +550,45 @@ def _adamw_case(ops, dev):
             assert torch.allclose(ema.cpu(), ema_ref, rtol=1e-6, atol=1e-7), (n, step)
 
 
+def _adamw_dev_case(ops, dev):
+    """sat_adamw_step_dev reads (lr, 1 - beta1^t, sqrt(1 - beta2^t), grad_scale, ema_decay) from a device buffer rewritten before each step
+    (the replayed HIP graph's step): bit-equal to sat_adamw_step given the same scalars, which it rounds on the host in fp32
+    (1.0f - powf(beta, t), sqrtf(...)) — p, m, v and the EMA shadow, three steps, sizes around the 4-element vector width."""
+    import numpy as np
+    b1, b2, eps, wd = 0.8, 0.95, 1e-6, 0.1
+    one = np.float32(1.0)
+    for n in (1, 3, 4, 1030, 4099):
+        gen = torch.Generator().manual_seed(100 + n)
+        p0 = torch.randn(n, generator=gen)
+        host = [p0.clone().to(dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev), p0.clone().to(dev)]      # p, m, v, ema
+        devs = [t.clone() for t in host]
+        hyper = torch.zeros(5, dtype=torch.float32, device=dev)
+        for step in (1, 2, 3):
+            g = torch.randn(n, generator=gen).to(dev)
+            lr, gscale, decay = 1e-2 / step, 0.5 + 0.125 * step, 1.0 - 0.1 / step
+            bc1 = one - np.power(np.float32(b1), np.float32(step))
+            bc2s = np.sqrt(one - np.power(np.float32(b2), np.float32(step)))
+            hyper.copy_(torch.tensor([lr, float(bc1), float(bc2s), gscale, decay], dtype=torch.float32))
+            ops.adamw_step(host[0], g, host[1], host[2], lr, b1, b2, eps, wd, step, grad_scale=gscale, ema=host[3], ema_decay=decay)
+            ops.adamw_step_dev(devs[0], g, devs[1], devs[2], hyper, b1, b2, eps, wd, ema=devs[3])
+            for name, a, b in zip("p m v ema".split(), devs, host):
+                assert torch.equal(a, b), (n, step, name, float((a - b).abs().max()))
+        assert not torch.equal(devs[0].cpu(), p0) and bool(torch.isfinite(devs[0]).all())
+    with pytest.raises(ValueError):
+        ops.adamw_step_dev(devs[0], g, devs[1], devs[2], hyper[:4], b1, b2, eps, wd)
+
+
 def test_adamw_kernel_simulator(emu):
     _adamw_case(emu, "cpu")
+
+
+def test_adamw_dev_kernel_simulator(emu):
+    _adamw_dev_case(emu, "cpu")
+
+
+@pytest.mark.gpu
+def test_adamw_dev_kernel_gpu(hip):
+    _adamw_dev_case(hip, "cuda")
 
 
 @pytest.mark.gpu
