@@ -365,7 +365,7 @@ int sat_allreduce_finalize(void* comm);
  * (statistics / softmax / accumulation always fp32).
  * ---------------------------------------------------------------------------------------------- */
 /* Attention.apply_attn (transformer.py:406-441): o = softmax(q k^T * scale) v, dense, non-causal, no mask;
- * grouped-query when Hkv < H (replaces repeat_interleave :408-411); head_dim must be 64.
+ * grouped-query when Hkv < H (replaces repeat_interleave :408-411); head_dim must be 64 (the forward also serves 128).
  *
  * sat_attn_prepare: src element (b,h,n,d) at b*sb + h*sh + n*sn + d (ELEMENT strides, d contiguous, fp32 or
  * bf16) -> bf16 planes zero-padded to Np = N rounded up to 64: row-major [B][H][Np][64] (rm_*) and/or transposed
@@ -373,6 +373,11 @@ int sat_allreduce_finalize(void* comm);
  * and the kernels then form every product as three bf16 MFMAs — the fp32-parity mode; bf16 sources use hi only. */
 int sat_attn_prepare(const void* src, long long sb, long long sh, long long sn, short* rm_hi, short* rm_lo,
                      short* tr_hi, short* tr_lo, int B, int H, int N, int Np, int dtype, void* stream);
+/* sat_attn_prepare with the head dim as an argument.  head_dim 64 is sat_attn_prepare; 128 writes [B][H][Np][128] and/or
+ * [B][H][128][Np] planes for the head dim 128 FORWARD (sat_attention_fwd with head_dim 128: fp32 and bf16, self- and grouped-query
+ * cross-attention, dtype 0 / 1 / 2; there is no backward and no short-key kernel at that head dim).  Any other head_dim is an error. */
+int sat_attn_prepare_hd(const void* src, long long sb, long long sh, long long sn, short* rm_hi, short* rm_lo,
+                        short* tr_hi, short* tr_lo, int B, int H, int N, int Np, int head_dim, int dtype, void* stream);
 /* forward: q_* row-major planes (B,H,Nqp,64), k_* row-major (B,Hkv,Nkp,64), vt_* TRANSPOSED (B,Hkv,64,Nkp);
  * o: (B, Nq, H*64) in the model dtype — heads merged; lse: (B, H, Nq) fp32 or NULL.  dtype 1 (bf16): a wave owns 64 queries when
  * Nq >= 2048 and 256-query workgroups still put two on every CU (the long context), else 32; dtype 2 / 3 force 32 / 64 (A/B, tests). */
@@ -445,6 +450,11 @@ int sat_rope_apply(void* t, const float* cs, long long sb, long long sn, long lo
 int sat_qk_norm_fwd(const void* x, long long xs, void* y, long long ys, const float* q_gamma, const float* q_beta,
                     const float* k_gamma, const float* k_beta, const float* cs, int tab_off, float* stat, int tokens, int ntok,
                     int nh, int hq, int mode, float eps, int dtype, void* stream);
+/* sat_qk_norm_fwd with the head dim as an argument.  head_dim 64 is sat_qk_norm_fwd; 128 (inference: there is no backward) normalises
+ * rows of 128 values with (128) tables and rotates the first 64 dims (NeoX pairs (d, d + 32)) with cs (tab_off + ntok, 32, 2). */
+int sat_qk_norm_fwd_hd(const void* x, long long xs, void* y, long long ys, const float* q_gamma, const float* q_beta,
+                       const float* k_gamma, const float* k_beta, const float* cs, int tab_off, float* stat, int tokens, int ntok,
+                       int nh, int hq, int mode, float eps, int head_dim, int dtype, void* stream);
 /* Backward: dy (gradient of y, same layout) is replaced IN PLACE by the gradient of x — inverse rotary, then the norm's backward with
  * x-hat recomputed from the raw x and stat.  "ln": part (sat_qk_norm_bwd_nblocks(tokens * nh), 2, 2, 64) fp32 receives per-block sums
  * [q | k][dgamma | dbeta] (reduce with sat_reduce_splits). */

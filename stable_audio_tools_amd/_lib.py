@@ -100,6 +100,7 @@ SIGNATURES = {
     "sat_spec_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     # attention.hip
     "sat_attn_prepare": (_I, [_P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "sat_attn_prepare_hd": (_I, [_P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sat_attention_fwd": (_I, [_P] * 8 + [_I] * 8 + [_F, _I, _P]),
     "sat_attention_rowdot": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "sat_attention_bwd": (_I, [_P] * 6 + [_I] * 8 + [_F, _I, _P]),
@@ -137,6 +138,7 @@ SIGNATURES = {
     "sat_rope_tables": (_I, [_P, _P, _I, _I, _F, _P]),
     "sat_rope_apply": (_I, [_P, _P, _L, _L, _L] + [_I] * 7 + [_P]),
     "sat_qk_norm_fwd": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _P] + [_I] * 5 + [_F, _I, _P]),
+    "sat_qk_norm_fwd_hd": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _P] + [_I] * 5 + [_F, _I, _I, _P]),
     "sat_qk_norm_bwd_nblocks": (_I, [_L]),
     "sat_qk_norm_bwd": (_I, [_P, _L, _P, _L, _P, _P, _P, _I, _P, _P] + [_I] * 6 + [_P]),
     "sat_swiglu": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),

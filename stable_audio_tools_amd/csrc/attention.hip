@@ -8,6 +8,7 @@
 // the autograd of all of it.
 //
 // Data flow
+//   (head dim 128, forward only: attention_hd128.h)
 //   sat_attn_prepare   (b,h,n,64) strided fp32|bf16  ->  bf16 "planes": row-major [B][H][Np][64] and/or
 //                      transposed [B][H][64][Np], Np = N rounded up to 64, zero padded.  fp32 sources
 //                      are split into hi + lo planes (x ~ hi + lo to ~2^-17): every product in the
@@ -1486,9 +1487,13 @@ __global__ void __launch_bounds__(256) sat_attn_rowdot_kernel(SatRowdotParams p)
 // ---------------------------------------------------------------------------------------------
 // host entry points
 // ---------------------------------------------------------------------------------------------
-static int sat_attn_check(int B, int H, int Hkv, int Nq, int Nk, int Nqp, int Nkp, int head_dim, int dtype, const char* who) {
+#include "attention_hd128.h"
+
+// fwd_only: the forward also serves head_dim == 128 (attention_hd128.h); everything else is head dim 64
+static int sat_attn_check(int B, int H, int Hkv, int Nq, int Nk, int Nqp, int Nkp, int head_dim, int dtype, const char* who, bool fwd_only = false) {
     if (B <= 0 || H <= 0 || Hkv <= 0 || Nq <= 0 || Nk <= 0) { sat_set_error(who); return 1; }
-    if (head_dim != SAT_ATT_D) { sat_set_error("attention: only head_dim == 64 (the Stable Audio DiT) is implemented"); return 1; }
+    if (head_dim == SAT_ATT_D2 && !fwd_only) { sat_set_error("attention: head_dim == 128 is inference-only (forward kernels; there is no backward at head dim 128)"); return 1; }
+    if (head_dim != SAT_ATT_D && head_dim != SAT_ATT_D2) { sat_set_error("attention: only head_dim == 64 (forward and backward) and 128 (forward) are implemented"); return 1; }
     if (H % Hkv != 0) { sat_set_error("attention: H must be a multiple of Hkv"); return 1; }
     if (Nqp < Nq || Nkp < Nk || Nqp % SAT_ATT_T || Nkp % SAT_ATT_T) { sat_set_error("attention: padded lengths must be multiples of 64 and cover N"); return 1; }
     if (dtype < 0 || dtype > 3) { sat_set_error("attention: dtype must be 0 (f32, split planes) or 1 (bf16; forward only: 2 / 3 = bf16 with 32 / 64 queries per wave forced)"); return 1; }
@@ -1500,11 +1505,23 @@ static int sat_attn_check(int B, int H, int Hkv, int Nq, int Nk, int Nqp, int Nk
 extern "C" int sat_attention_fwd(const short* q_hi, const short* q_lo, const short* k_hi, const short* k_lo,
                                  const short* vt_hi, const short* vt_lo, void* o, float* lse, int B, int H, int Hkv,
                                  int Nq, int Nk, int Nqp, int Nkp, int head_dim, float scale, int dtype, void* stream) {
-    if (sat_attn_check(B, H, Hkv, Nq, Nk, Nqp, Nkp, head_dim, dtype, "sat_attention_fwd: empty shape")) return 1;
+    if (sat_attn_check(B, H, Hkv, Nq, Nk, Nqp, Nkp, head_dim, dtype, "sat_attention_fwd: empty shape", true)) return 1;
     SatAttnParams p{};
     p.q_rm[0] = q_hi; p.q_rm[1] = q_lo; p.k_rm[0] = k_hi; p.k_rm[1] = k_lo; p.v_tr[0] = vt_hi; p.v_tr[1] = vt_lo;
     p.o = o; p.lse = lse; p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = Nq; p.Nk = Nk; p.Nqp = Nqp; p.Nkp = Nkp; p.scale = scale;
     dim3 grid(sat_cdiv(Nq, 128), H, B);
+    if (head_dim == SAT_ATT_D2) {      // one kernel per dtype: the 64-query and the short-key kernels are head dim 64 only
+        if (dtype == 3) { sat_set_error("sat_attention_fwd: dtype 3 (64 queries per wave) exists at head_dim == 64 only"); return 1; }
+        // a V^T tile is 128 rows of a transposed plane behind one 32-bit buffer offset
+        if (Nkp >= (1 << 23)) { sat_set_error("attention: head_dim == 128 serves fewer than 2^23 keys"); return 1; }
+        // bf16: 8 waves (256 queries) per workgroup when such workgroups still give every CU one, else 4 (profiles/attn_head_dim128/README.md)
+        // (dtype 2 forces 4: A/B runs and the tests' second implementation)
+        const bool w8 = dtype == 1 && (long long)sat_cdiv(Nq, 256) * H * B >= sat_cu_count();
+        if (dtype == 0) SAT_LAUNCH((sat_attn_fwd128_kernel<float, 2, 4>), grid, dim3(256), stream, p);
+        else if (w8) SAT_LAUNCH((sat_attn_fwd128_kernel<short, 1, 8>), dim3(sat_cdiv(Nq, 256), H, B), dim3(512), stream, p);
+        else SAT_LAUNCH((sat_attn_fwd128_kernel<short, 1, 4>), grid, dim3(256), stream, p);
+        return sat_check_launch("sat_attention_fwd");
+    }
     if (dtype == 0) {
         SAT_LAUNCH((sat_attn_fwd_kernel<float, 2>), grid, dim3(256), stream, p);
     } else {
@@ -1518,6 +1535,21 @@ extern "C" int sat_attention_fwd(const short* q_hi, const short* q_lo, const sho
         else SAT_LAUNCH((sat_attn_fwd_kernel<short, 1>), grid, dim3(256), stream, p);
     }
     return sat_check_launch("sat_attention_fwd");
+}
+
+// sat_attn_prepare with the head dim as an argument: 64 is sat_attn_prepare itself, 128 writes [B][H][Np][128] / [B][H][128][Np] planes
+extern "C" int sat_attn_prepare_hd(const void* src, long long sb, long long sh, long long sn, short* rm_hi, short* rm_lo,
+                                   short* tr_hi, short* tr_lo, int B, int H, int N, int Np, int head_dim, int dtype, void* stream) {
+    if (head_dim == SAT_ATT_D) return sat_attn_prepare(src, sb, sh, sn, rm_hi, rm_lo, tr_hi, tr_lo, B, H, N, Np, dtype, stream);
+    if (head_dim != SAT_ATT_D2) { sat_set_error("sat_attn_prepare_hd: head_dim must be 64 or 128"); return 1; }
+    if (B <= 0 || H <= 0 || N <= 0) { sat_set_error("sat_attn_prepare_hd: empty shape"); return 1; }
+    if (Np < N || (Np % SAT_ATT_T) != 0) { sat_set_error("sat_attn_prepare_hd: Np must be N rounded up to a multiple of 64"); return 1; }
+    if (dtype != 0 && dtype != 1) { sat_set_error("sat_attn_prepare_hd: dtype must be 0 (f32) or 1 (bf16)"); return 1; }
+    SatPrepParams p{src, sb, sh, sn, rm_hi, rm_lo, tr_hi, tr_lo, B, H, N, Np};
+    dim3 grid(Np / SAT_ATT_T, H, B);
+    if (dtype == 0) SAT_LAUNCH(sat_attn_prepare128_kernel<float>, grid, dim3(256), stream, p);
+    else SAT_LAUNCH(sat_attn_prepare128_kernel<short>, grid, dim3(256), stream, p);
+    return sat_check_launch("sat_attn_prepare_hd");
 }
 
 extern "C" int sat_attention_rowdot(const void* dout, const void* out, float* dsum, int B, int H, int Nq, int dtype,

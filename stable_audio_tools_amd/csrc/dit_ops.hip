@@ -797,6 +797,74 @@ extern "C" int sat_qk_norm_fwd(const void* x, long long xs, void* y, long long y
     return sat_check_launch("sat_qk_norm_fwd");
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same forward at head dim 128 (inference only: there is no backward at that head dim).  A row is 128 values: 32 lanes per row, 4
+// columns per lane, 8 rows per workgroup, the row statistics are 32-lane butterflies.  The rotary covers the first 64 dims
+// (RotaryEmbedding(max(dim_heads // 2, 32)): half = 32, NeoX pairs (d, d + 32)), so the partner columns c ^ 32 live 8 lanes away and
+// the table is (Ntab, 32, 2).
+// ------------------------------------------------------------------------------------------------
+SAT_DEVICE float sat_group32_sum(float v) {
+    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+template <typename T>
+__global__ void __launch_bounds__(256) sat_qk_norm128_fwd_kernel(SatQkNormParams p) {
+    const int c = (threadIdx.x & 31) * 4;
+    const long long row = (long long)blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (row >= p.rows) return;            // a whole 32-lane group leaves together: the butterflies below stay inside a group
+    const long long tok = row / p.nh;
+    const int j = (int)(row - tok * p.nh);
+    f32x4 v = SatRow4<T>::ld(p.x, tok * p.xs + j * 128 + c);
+    float mean = 0.f, rs;
+    if (p.mode == 1) {
+        mean = sat_group32_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 128.0f);
+        v -= mean;
+    }
+    const float ss = sat_group32_sum((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
+    rs = (p.mode == 1) ? 1.0f / sqrtf(ss * (1.0f / 128.0f) + p.eps) : 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+    v *= rs;
+    if (p.mode == 1) {
+        const float* g = j < p.hq ? p.gq : p.gk;
+        const float* b = j < p.hq ? p.bq : p.bk;
+        v = v * *reinterpret_cast<const f32x4*>(g + c) + *reinterpret_cast<const f32x4*>(b + c);
+    }
+    if (p.cs) {
+        f32x4 pv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pv[e] = __shfl_xor(v[e], 8);
+        if (c < 64) {
+            const float* t = p.cs + ((p.tab_off + tok % p.ntok) * 32 + (c & 31)) * 2;
+            const f32x4 cs0 = *reinterpret_cast<const f32x4*>(t), cs1 = *reinterpret_cast<const f32x4*>(t + 4);
+            const float co[4] = {cs0[0], cs0[2], cs1[0], cs1[2]}, si[4] = {cs0[1], cs0[3], cs1[1], cs1[3]};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = (c < 32) ? v[e] * co[e] - pv[e] * si[e] : v[e] * co[e] + pv[e] * si[e];
+        }
+    }
+    SatRow4<T>::st(p.y, tok * p.ys + j * 128 + c, v);
+    if (p.stat && c == 0) {
+        p.stat[row] = (p.mode == 1) ? mean : rs;
+        if (p.mode == 1) p.stat[p.rows + row] = rs;
+    }
+}
+
+// sat_qk_norm_fwd with the head dim as an argument: 64 is sat_qk_norm_fwd itself; 128: rows of 128 values, tables (128,), cs (tab_off + ntok, 32, 2)
+extern "C" int sat_qk_norm_fwd_hd(const void* x, long long xs, void* y, long long ys, const float* q_gamma, const float* q_beta,
+                                  const float* k_gamma, const float* k_beta, const float* cs, int tab_off, float* stat, int tokens, int ntok,
+                                  int nh, int hq, int mode, float eps, int head_dim, int dtype, void* stream) {
+    if (head_dim == 64) return sat_qk_norm_fwd(x, xs, y, ys, q_gamma, q_beta, k_gamma, k_beta, cs, tab_off, stat, tokens, ntok, nh, hq, mode, eps, dtype, stream);
+    if (head_dim != 128) { sat_set_error("sat_qk_norm_fwd_hd: head_dim must be 64 or 128"); return 1; }
+    SatQkNormParams p{};
+    p.x = x; p.y = y; p.gq = q_gamma; p.bq = q_beta; p.gk = k_gamma; p.bk = k_beta; p.cs = cs; p.stat = stat;
+    p.xs = xs; p.ys = ys; p.ntok = ntok; p.nh = nh; p.hq = hq; p.tab_off = tab_off; p.mode = mode; p.eps = eps;
+    if (sat_qk_norm_check(p, tokens, dtype, x, y, true, "sat_qk_norm_fwd_hd: bad shape")) return 1;
+    if (xs < (long long)nh * 128 || ys < (long long)nh * 128) { sat_set_error("sat_qk_norm_fwd_hd: rows must hold nh * 128 elements"); return 1; }
+    p.rows = (long long)tokens * nh;
+    dim3 grid((unsigned)sat_cdivll(p.rows, 8));
+    if (dtype == 0) SAT_LAUNCH(sat_qk_norm128_fwd_kernel<float>, grid, dim3(256), stream, p);
+    else SAT_LAUNCH(sat_qk_norm128_fwd_kernel<short>, grid, dim3(256), stream, p);
+    return sat_check_launch("sat_qk_norm_fwd_hd");
+}
+
 extern "C" int sat_qk_norm_bwd_nblocks(long long rows) { return (int)sat_cdivll(rows, 16 * SAT_QKN_BWD_ITERS); }
 
 // dy (gradient of sat_qk_norm_fwd's y, same layout) -> gradient of x, IN PLACE.  x, stat: the forward's input and statistics.

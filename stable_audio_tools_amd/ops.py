@@ -1019,13 +1019,15 @@ class SatOps:
         return 0 if dt == torch.float32 else 1
 
     def attn_planes(self, t, row_major=True, transposed=False):
-        """(B, H, N, 64) strided fp32|bf16 (head dim contiguous) -> bf16 planes, zero padded to Np = ceil64(N):
-        dict with 'rm' = (hi, lo) of shape (B, H, Np, 64) and/or 'tr' = (hi, lo) of shape (B, H, 64, Np);
+        """(B, H, N, D) strided fp32|bf16 (head dim D = 64 or 128 contiguous) -> bf16 planes, zero padded to Np = ceil64(N):
+        dict with 'rm' = (hi, lo) of shape (B, H, Np, D) and/or 'tr' = (hi, lo) of shape (B, H, D, Np);
         lo is None for bf16 sources."""
         dt = self._dt(t)
         if t.stride(3) != 1:
             raise ValueError("head dim must be contiguous")
         b, h, n, d = t.shape
+        if d not in self.ATTN_HEAD_DIMS:
+            raise NotImplementedError(f"attention planes exist for head dim 64 and 128 (forward only), got {d}")
         npad = (n + 63) // 64 * 64
         split = dt == 0
 
@@ -1033,16 +1035,25 @@ class SatOps:
             return torch.empty(shape, dtype=torch.int16, device=t.device) if want else None
         rm_hi, rm_lo = alloc((b, h, npad, d), row_major), alloc((b, h, npad, d), row_major and split)
         tr_hi, tr_lo = alloc((b, h, d, npad), transposed), alloc((b, h, d, npad), transposed and split)
-        self._chk(self.lib.sat_attn_prepare(_ptr(t), t.stride(0), t.stride(1), t.stride(2), _ptr(rm_hi), _ptr(rm_lo),
-                                            _ptr(tr_hi), _ptr(tr_lo), b, h, n, npad, dt, self._stream(t)))
-        return {"rm": (rm_hi, rm_lo), "tr": (tr_hi, tr_lo), "n": n, "np": npad, "dt": dt}
+        if d == 64:
+            self._chk(self.lib.sat_attn_prepare(_ptr(t), t.stride(0), t.stride(1), t.stride(2), _ptr(rm_hi), _ptr(rm_lo),
+                                                _ptr(tr_hi), _ptr(tr_lo), b, h, n, npad, dt, self._stream(t)))
+        else:
+            self._chk(self.lib.sat_attn_prepare_hd(_ptr(t), t.stride(0), t.stride(1), t.stride(2), _ptr(rm_hi), _ptr(rm_lo),
+                                                   _ptr(tr_hi), _ptr(tr_lo), b, h, n, npad, d, dt, self._stream(t)))
+        return {"rm": (rm_hi, rm_lo), "tr": (tr_hi, tr_lo), "n": n, "np": npad, "dt": dt, "d": d}
 
     def attention(self, q, k, v, scale, need_lse=False, return_planes=False):
-        """q: (B, H, Nq, 64) k, v: (B, Hkv, Nk, 64) — any strides with the head dim contiguous.
-        Returns o: (B, Nq, H*64) [, lse (B, H, Nq) fp32] [, planes dict for the backward]."""
+        """q: (B, H, Nq, D) k, v: (B, Hkv, Nk, D) — any strides with the head dim contiguous; D = 64, or 128 (inference only: the
+        general forward kernel in fp32 and bf16; no planes for a backward, no short-key kernel).
+        Returns o: (B, Nq, H*D) [, lse (B, H, Nq) fp32] [, planes dict for the backward]."""
         dt = self._dt(q, k, v)
         b, h, nq, d = q.shape
         _, hk, nk, _ = k.shape
+        if k.shape[3] != d or v.shape[3] != d:
+            raise ValueError("attention: q, k and v must share the head dim")
+        if d != 64 and return_planes:
+            raise NotImplementedError(f"attention: head dim {d} is inference-only (there is no backward to keep planes for)")
         qp = self.attn_planes(q, row_major=True, transposed=return_planes)
         kp = self.attn_planes(k, row_major=True, transposed=return_planes)
         vp = self.attn_planes(v, row_major=return_planes, transposed=True)
@@ -1054,7 +1065,7 @@ class SatOps:
         else:
             self._chk(self.lib.sat_attention_fwd(_ptr(qp["rm"][0]), _ptr(qp["rm"][1]), _ptr(kp["rm"][0]), _ptr(kp["rm"][1]),
                                                  _ptr(vp["tr"][0]), _ptr(vp["tr"][1]), _ptr(o), _ptr(lse), b, h, hk, nq, nk,
-                                                 qp["np"], kp["np"], d, float(scale), self._fwd_dtype(dt), self._stream(q)))
+                                                 qp["np"], kp["np"], d, float(scale), self._fwd_dtype(dt) if d == 64 or self.attn_q64 is False else dt, self._stream(q)))
         out = (o,)
         if need_lse or return_planes:
             out += (lse,)
@@ -1066,6 +1077,8 @@ class SatOps:
         """Gradients (dq (B,H,Nq,64), dk, dv (B,Hkv,Nk,64)) in the dtype of `o`; `planes` from attention(return_planes=True).
         out: optional (dq, dk, dv) contiguous tensors of those shapes to write into (e.g. slices of one buffer)."""
         dt = self._dt(o, do)
+        if planes["q"].get("d", 64) != 64:
+            raise NotImplementedError("attention_bwd: head dim 128 is inference-only")
         b, nq, hd = o.shape
         h = hd // 64
         do = do.contiguous()
@@ -1105,6 +1118,8 @@ class SatOps:
     cast_pair = True        # both transposed operands of a weight-gradient GEMM from one launch (sat_cast_bf16_tpair); False: two sat_cast_bf16 launches
     # bf16 self-attention forward: None = the library picks 32 or 64 queries per wave by grid size (sat_attention_fwd), False / True force
     # the 32- / 64-query kernel (A/B runs: bench.py --ops-set attn_q64=1; the kernel tests run both)
+    # (head dim 128 has one bf16 kernel in two workgroup shapes, 4 or 8 waves, picked by grid size: False forces 4, None and True leave the choice
+    # to the library)
     attn_q64 = None
 
     def _fwd_dtype(self, dt):
@@ -1191,41 +1206,63 @@ class SatOps:
         return t
 
     QK_NORM_MODES = {"ln": 1, "l2": 2}
+    ATTN_HEAD_DIMS = (64, 128)      # 128: the inference kernels only (csrc/attention_hd128.h, sat_qk_norm_fwd_hd)
 
-    def _qk_tables(self, mode, tables, nh, hq):
-        """(mode code, [q gamma, q beta, k gamma, k beta]) for the qk-norm kernels: fp32 (64,) tensors for "ln", Nones for "l2"."""
+    def _qk_tables(self, mode, tables, nh, hq, d=64):
+        """(mode code, [q gamma, q beta, k gamma, k beta]) for the qk-norm kernels: fp32 (d,) tensors for "ln", Nones for "l2"."""
         code = self.QK_NORM_MODES[mode]
         tables = list(tables) if tables is not None else [None] * 4
         if code == 1:
             need = ([0, 1] if hq > 0 else []) + ([2, 3] if hq < nh else [])
             for i in need:
-                if tables[i] is None or tables[i].numel() != 64:
-                    raise ValueError("qk_norm 'ln' needs (64,) fp32 gamma / beta tables")
+                if tables[i] is None or tables[i].numel() != d:
+                    raise ValueError(f"qk_norm 'ln' needs ({d},) fp32 gamma / beta tables")
             self._f32(*tables)
         else:
             tables = [None] * 4
         return code, tables
 
-    def qk_norm(self, x, nh, hq, mode, tables=None, cs=None, eps=1e-6, out=None, save_stats=False):
-        """Per-head q / k normalisation + rotary (sat_qk_norm_fwd).  x: (B, N, C) with C >= nh*64, last dim contiguous: the first nh heads
+    def _qk_head_dim(self, tables, cs, head_dim):
+        """The head dim of a qk_norm call: given, else read from the "ln" tables ((d,) each), else from the rotary table (the reference's
+        RotaryEmbedding(max(d // 2, 32)): 16 pairs at 64, 32 at 128), else 64."""
+        if head_dim is None:
+            given = [t for t in (tables or ()) if t is not None]
+            if given:
+                head_dim = given[0].numel()
+            elif cs is not None:
+                head_dim = {16: 64, 32: 128}.get(cs.shape[1])
+            else:
+                head_dim = 64
+        if head_dim not in self.ATTN_HEAD_DIMS or (cs is not None and cs.shape[1] != head_dim // 4):
+            raise ValueError("qk_norm: head dim 64 (rotary table (N, 16, 2)) or 128 ((N, 32, 2)) only")
+        return head_dim
+
+    def qk_norm(self, x, nh, hq, mode, tables=None, cs=None, eps=1e-6, out=None, save_stats=False, head_dim=None):
+        """Per-head q / k normalisation + rotary (sat_qk_norm_fwd; sat_qk_norm_fwd_hd at head dim 128, which is inference-only: read 64 as
+        the head dim below — head_dim, or what the tables / the rotary table say).  x: (B, N, C) with C >= nh*64, last dim contiguous: the first nh heads
         of every token are normalised ("ln": LayerNorm over the 64 head dims with tables = (q gamma, q beta, k gamma, k beta), heads < hq
         take the q pair; "l2": x / max(|x|, 1e-12)), then rotated with cs ((>= N, 16, 2) table or None), and written to `out` (same
         batch / token shape, C' >= nh*64; default: a new tensor like x whose columns past nh*64 are NOT written).
         Returns out, or (out, stat) with save_stats: fp32, (2, B*N*nh) = mean | rstd for "ln", (1, B*N*nh) = 1 / max(|x|, 1e-12) for "l2"."""
         dt = self._dt(x, out)
         b, n, c = x.shape
+        d = self._qk_head_dim(tables if mode == "ln" else None, cs, head_dim)
         if out is None:
             out = torch.empty_like(x, memory_format=torch.contiguous_format)
         if x.stride(2) != 1 or out.stride(2) != 1 or x.stride(0) != n * x.stride(1) or out.stride(0) != n * out.stride(1) \
-                or out.shape[:2] != x.shape[:2] or min(c, out.shape[2]) < nh * 64:
+                or out.shape[:2] != x.shape[:2] or min(c, out.shape[2]) < nh * d:
             raise ValueError("qk_norm: bad layout")
-        code, (gq, bq, gk, bk) = self._qk_tables(mode, tables, nh, hq)
+        code, (gq, bq, gk, bk) = self._qk_tables(mode, tables, nh, hq, d)
         if cs is not None:
             self._f32(cs)
         stat = torch.empty(2 if code == 1 else 1, b * n * nh, dtype=torch.float32, device=x.device) if save_stats else None
-        self._chk(self.lib.sat_qk_norm_fwd(_ptr(x), x.stride(1), _ptr(out), out.stride(1), _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk), _ptr(cs),
-                                           (cs.shape[0] - n) if cs is not None else 0, _ptr(stat), b * n, n, nh, hq, code, float(eps), dt,
-                                           self._stream(x)))
+        tab_off = (cs.shape[0] - n) if cs is not None else 0
+        if d == 64:
+            self._chk(self.lib.sat_qk_norm_fwd(_ptr(x), x.stride(1), _ptr(out), out.stride(1), _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk), _ptr(cs),
+                                               tab_off, _ptr(stat), b * n, n, nh, hq, code, float(eps), dt, self._stream(x)))
+        else:
+            self._chk(self.lib.sat_qk_norm_fwd_hd(_ptr(x), x.stride(1), _ptr(out), out.stride(1), _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk),
+                                                  _ptr(cs), tab_off, _ptr(stat), b * n, n, nh, hq, code, float(eps), d, dt, self._stream(x)))
         return (out, stat) if save_stats else out
 
     def qk_norm_bwd_(self, dy, x, stat, nh, hq, mode, tables=None, cs=None):

@@ -476,8 +476,9 @@ class Attention(nn.Module):
             raise ValueError(f'qk_norm must be one of ["l2", "ln", "none"], got {qk_norm}')
         if qk_norm == "dyt":
             raise NotImplementedError('qk_norm="dyt" (DynamicTanh) is not on the HIP path; "ln" and "l2" are')
-        if dim_heads != 64:
-            raise NotImplementedError("the HIP attention kernel is specialised for head dim 64 (every Stable Audio DiT config)")
+        if dim_heads not in (64, 128):
+            raise NotImplementedError("the HIP attention kernels serve head dim 64 (every Stable Audio DiT config; training and inference) "
+                                      "and head dim 128 (inference only)")
         self.dim, self.dim_heads = dim, dim_heads
         dim_kv = dim_context if dim_context is not None else dim
         self.num_heads = dim // dim_heads
@@ -529,6 +530,50 @@ class Attention(nn.Module):
             return ops.gemm_heads_fp8(qx, qw, alpha, cs, heads, nb, ntok, sec0, nsec, reuse=tag, col_alpha=calpha)
         return ops.gemm_heads_bf16(x2, lin.lowp_weight(), cs, heads, nb, ntok, sec0, nsec, reuse=tag)
 
+    def _forward_hd128(self, x, kv_input, rotary_pos_emb, res, norm):
+        """Head dim 128 (inference only; fp32 and bf16): projection through the Linear, then the standalone norm + rotary kernel
+        (sat_qk_norm_fwd_hd) or the in-place rotary, then plane preparation and the forward kernel of csrc/attention_hd128.h
+        (ops.attention), then to_out with the residual epilogue.  The projection-epilogue fusion of the head dim 64 bf16 path
+        (gemm_heads_bf16) is not built at 128."""
+        if torch.is_grad_enabled():
+            raise NotImplementedError("head dim 128 is inference-only (there are no backward kernels at this head dim): run the model under torch.no_grad()")
+        cross = hasattr(self, "to_q")
+        first = self.to_q if cross else self.to_qkv
+        if isinstance(x, _linear.Fp8Rows) or first.fp8 or (cross and self.to_kv.fp8):
+            raise NotImplementedError("head dim 128 on an fp8 input projection is not built (keep to_qkv / to_q / to_kv in bf16)")
+        ops = _ops()
+        h, kv_h, dh = self.num_heads, self.kv_heads, self.dim_heads
+        b, n, _ = x.shape
+        if cross:
+            m = kv_input.shape[1]
+            q2, kv = self.to_q(x).contiguous(), self.to_kv(kv_input).contiguous()
+            if norm is not None:
+                mode, tabs = norm
+                q2 = ops.qk_norm(q2, h, h, mode, tabs, None, head_dim=dh)
+                kn = torch.empty(b, m, kv_h * dh, dtype=kv.dtype, device=kv.device)
+                k2 = ops.qk_norm(kv, kv_h, 0, mode, tabs, None, out=kn, head_dim=dh)
+            else:
+                k2 = kv[..., :kv_h * dh]
+            q = q2.view(b, n, h, dh).permute(0, 2, 1, 3)
+            k = k2.unflatten(-1, (kv_h, dh)).permute(0, 2, 1, 3)
+            v = kv[..., kv_h * dh:].unflatten(-1, (kv_h, dh)).permute(0, 2, 1, 3)
+        else:
+            cs = rotary_pos_emb[0] if rotary_pos_emb is not None else None
+            qkv = self.to_qkv(x).contiguous()
+            hd = h * dh
+            if norm is not None:
+                mode, tabs = norm
+                qk = torch.empty(b, n, 2 * hd, dtype=qkv.dtype, device=qkv.device)
+                ops.qk_norm(qkv, 2 * h, h, mode, tabs, cs, out=qk, head_dim=dh)
+            else:
+                qk = qkv[..., :2 * hd]
+                if cs is not None:      # in place on the projection's own output: nothing else reads it
+                    ops.rope_apply_(qk.unflatten(-1, (2 * h, dh)), cs)
+            q = qk[..., :hd].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
+            k = qk[..., hd:].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
+            v = qkv[..., 2 * hd:].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
+        return self.to_out(ops.attention(q, k, v, self.scale), res=res)
+
     def forward(self, x, context=None, rotary_pos_emb=None, causal=None, res=None, **unsupported):
         """res: the residual stream, added in the output projection's epilogue (x = x + attn(...), transformer.py:703-707)."""
         for k, v in unsupported.items():
@@ -544,6 +589,8 @@ class Attention(nn.Module):
         norm = self._norm()
         if norm is not None and (isinstance(x, _linear.Fp8Rows) or first.fp8 or (cross and self.to_kv.fp8)):
             raise NotImplementedError("qk_norm on an fp8 input projection: the fp8 heads GEMM has no norm epilogue (keep to_qkv / to_q / to_kv in bf16)")
+        if dh == 128:
+            return self._forward_hd128(x, kv_input, rotary_pos_emb, res, norm)
         if not torch.is_grad_enabled() and _lowp(x, first.weight) and first.lowp_weight() is not None \
                 and (not cross or self.to_kv.lowp_weight() is not None):
             # inference, bf16: head split, rotary and the attention kernel's operand planes come straight out of the
@@ -615,6 +662,12 @@ class Attention(nn.Module):
         return self.to_out(out, res=res)
 
 
+def _fp8_rows_for(attn, lin):
+    """The projection a LayerNorm may hand fp8-quantised rows to (LayerNorm.forward(fp8_for=...)): none at head dim 128, whose input
+    projections are plain Linears (Attention._forward_hd128 takes no Fp8Rows)."""
+    return lin if attn.dim_heads == 64 else None
+
+
 class TransformerBlock(nn.Module):
     def __init__(self, dim, dim_heads=64, cross_attend=False, dim_context=None, global_cond_dim=None, causal=False,
                  zero_init_branch_outputs=True, conformer=False, layer_ix=-1, remove_norms=False, add_rope=False,
@@ -650,10 +703,10 @@ class TransformerBlock(nn.Module):
             mod = (self.to_scale_shift_gate + global_cond).to(x.dtype).contiguous()   # (B, 6D)
             scale_self, shift_self, gate_self = mod[:, 0:d], mod[:, d:2 * d], mod[:, 2 * d:3 * d]
             scale_ff, shift_ff, gate_ff = mod[:, 3 * d:4 * d], mod[:, 4 * d:5 * d], mod[:, 5 * d:6 * d]
-            h = self.self_attn(self.pre_norm(x, scale_self, shift_self, fp8_for=self.self_attn.to_qkv), rotary_pos_emb=rotary_pos_emb)
+            h = self.self_attn(self.pre_norm(x, scale_self, shift_self, fp8_for=_fp8_rows_for(self.self_attn, self.self_attn.to_qkv)), rotary_pos_emb=rotary_pos_emb)
             x = _GateResidualFn.apply(h, gate_self, x)                           # h*sigmoid(1-gate)+x  (:684-686)
             if context is not None and self.cross_attend:
-                x = self.cross_attn(self.cross_attend_norm(x, fp8_for=self.cross_attn.to_q), context=context, res=x)   # never modulated (:688-689)
+                x = self.cross_attn(self.cross_attend_norm(x, fp8_for=_fp8_rows_for(self.cross_attn, self.cross_attn.to_q)), context=context, res=x)   # never modulated (:688-689)
             h = self.ff(self.ff_norm(x, scale_ff, shift_ff, fp8_for=self.ff.ff[0].proj))
             x = _GateResidualFn.apply(h, gate_ff, x)
         else:
@@ -667,9 +720,9 @@ class TransformerBlock(nn.Module):
                     x = self.cross_attn(h, context=context, res=xr)
                 h, xr = self.ff_norm.with_residual(x)
                 return self.ff(h, res=xr)
-            x = self.self_attn(self.pre_norm(x, fp8_for=self.self_attn.to_qkv), rotary_pos_emb=rotary_pos_emb, res=x)   # residual adds live in
+            x = self.self_attn(self.pre_norm(x, fp8_for=_fp8_rows_for(self.self_attn, self.self_attn.to_qkv)), rotary_pos_emb=rotary_pos_emb, res=x)   # residual adds live in
             if context is not None and self.cross_attend:                                                                 # the output projections' epilogues
-                x = self.cross_attn(self.cross_attend_norm(x, fp8_for=self.cross_attn.to_q), context=context, res=x)
+                x = self.cross_attn(self.cross_attend_norm(x, fp8_for=_fp8_rows_for(self.cross_attn, self.cross_attn.to_q)), context=context, res=x)
             x = self.ff(self.ff_norm(x, fp8_for=self.ff.ff[0].proj), res=x)
         return x
 
