@@ -1,6 +1,6 @@
 // attention.hip — dense non-causal scaled-dot-product attention for the DiT (head dim 64), flash
 // style on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16): forward, and backward (dQ / dK,dV),
-// self- and grouped-query cross-attention.
+// self- and grouped-query cross-attention.  Plane preparation and the forward also serve head dim 128.
 //
 // Replaces Attention.apply_attn (stable_audio_tools/models/transformer.py:406-441): flash_attn_func /
 // F.scaled_dot_product_attention with scale 1/sqrt(d), no mask (masks are disabled by the caller,
@@ -8,9 +8,9 @@
 // the autograd of all of it.
 //
 // Data flow
-//   (head dim 128, forward only: attention_hd128.h)
-//   sat_attn_prepare   (b,h,n,64) strided fp32|bf16  ->  bf16 "planes": row-major [B][H][Np][64] and/or
-//                      transposed [B][H][64][Np], Np = N rounded up to 64, zero padded.  fp32 sources
+//   (D = head dim: 64, or 128 in plane preparation and the forward — sat_attn_prepare_hd, sat_attn_fwd_kernel; inference only)
+//   sat_attn_prepare   (b,h,n,D) strided fp32|bf16  ->  bf16 "planes": row-major [B][H][Np][D] and/or
+//                      transposed [B][H][D][Np], Np = N rounded up to 64, zero padded.  fp32 sources
 //                      are split into hi + lo planes (x ~ hi + lo to ~2^-17): every product in the
 //                      kernels is then three MFMAs (hi*hi + hi*lo + lo*hi) with fp32 accumulation —
 //                      the 1e-3 "rel fp32" parity mode.  bf16 sources give one plane, one MFMA.
@@ -24,9 +24,10 @@
 // its B operand: the MFMA k-slot order is defined to be the accumulator row order
 // (slot (hi,e) of step u <-> row 16u + 4hi + (e&3) + 8(e>>2)) and the LDS-side operand is read in that
 // same order.
+#include <cstdio>
 #include "sat_device.h"
 
-#define SAT_ATT_D 64
+#define SAT_ATT_D 64              // head dim of every kernel that is not templated on it (the backward, the 64-query forward, cross)
 #define SAT_ATT_T 64              // tile width (keys in fwd/dQ, queries in dK/dV)
 #define SAT_ATT_ROW 72            // bf16 per LDS row (64 + 8 pad -> 144 B stride, conflict-free b128/b64)
 
@@ -39,8 +40,8 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 struct SatPrepParams {
     const void* src;            // element (b,h,n,d) at b*sb + h*sh + n*sn + d
     long long sb, sh, sn;
-    short* rm_hi; short* rm_lo; // [B][H][Np][64]   (null = skip)
-    short* tr_hi; short* tr_lo; // [B][H][64][Np]
+    short* rm_hi; short* rm_lo; // [B][H][Np][D]   (null = skip)
+    short* tr_hi; short* tr_lo; // [B][H][D][Np]
     int B, H, N, Np;
 };
 
@@ -48,21 +49,22 @@ template <typename T> struct SatSrc;
 template <> struct SatSrc<float> { static SAT_DEVICE float at(const void* p, long long i) { return ((const float*)p)[i]; } };
 template <> struct SatSrc<short> { static SAT_DEVICE float at(const void* p, long long i) { return sat_bf16_to_f32(((const short*)p)[i]); } };
 
-// One 64 (n) x 64 (d) tile per workgroup; a thread converts 8 consecutive d of one row (16-byte plane stores), the
-// transposed planes go through an LDS tile and are written 8 consecutive n at a time.
-template <typename T>
+// One 64 (n) x D (d) tile per workgroup, D = 64 or 128; a thread converts 8 consecutive d of one row (16-byte loads where the strides
+// allow, 16-byte plane stores), the transposed planes go through an LDS tile and are written 8 consecutive n at a time.
+template <typename T, int D>
 __global__ void __launch_bounds__(256) sat_attn_prepare_kernel(SatPrepParams p) {
-    __shared__ __attribute__((aligned(16))) short t_hi[SAT_ATT_T][SAT_ATT_D + 8];   // [n][d]
-    __shared__ __attribute__((aligned(16))) short t_lo[SAT_ATT_T][SAT_ATT_D + 8];
+    __shared__ __attribute__((aligned(16))) short t_hi[SAT_ATT_T][D + 8];   // [n][d]
+    __shared__ __attribute__((aligned(16))) short t_lo[SAT_ATT_T][D + 8];
+    constexpr int PARTS = D / 8;
     const int n0 = blockIdx.x * SAT_ATT_T, h = blockIdx.y, b = blockIdx.z;
     const long long base = (long long)b * p.sb + (long long)h * p.sh;
-    const size_t plane = ((size_t)b * p.H + h) * (size_t)p.Np * SAT_ATT_D;
+    const size_t plane = ((size_t)b * p.H + h) * (size_t)p.Np * D;
     const bool want_tr = p.tr_hi != nullptr || p.tr_lo != nullptr;
     const bool vec_src = ((p.sn & 7) == 0) && ((p.sb & 7) == 0) && ((p.sh & 7) == 0) &&
                          (((uintptr_t)p.src & 15) == 0);                              // 16-byte loads allowed
-    for (int i = threadIdx.x; i < SAT_ATT_T * SAT_ATT_D / 8; i += 256) {
-        const int r = i >> 3, d0 = (i & 7) * 8;
-        const int n = n0 + r;
+    for (int i = threadIdx.x; i < SAT_ATT_T * PARTS; i += 256) {
+        const int r = i / PARTS, d0 = (i % PARTS) * 8;
+        const int n = n0 + r;                                                         // < Np: the grid covers Np / 64 tiles
         float x[8];
         if (n < p.N) {
             const long long off = base + (long long)n * p.sn + d0;
@@ -92,7 +94,7 @@ __global__ void __launch_bounds__(256) sat_attn_prepare_kernel(SatPrepParams p) 
 #pragma unroll
         for (int j = 0; j < 4; ++j) sat_split2_pk(x[2 * j], x[2 * j + 1], &wh[j], &wl[j]);
         const u32x4 vh{wh[0], wh[1], wh[2], wh[3]}, vl{wl[0], wl[1], wl[2], wl[3]};
-        const size_t o = plane + (size_t)n * SAT_ATT_D + d0;
+        const size_t o = plane + (size_t)n * D + d0;
         if (p.rm_hi) *reinterpret_cast<u32x4*>(p.rm_hi + o) = vh;
         if (p.rm_lo) *reinterpret_cast<u32x4*>(p.rm_lo + o) = vl;
         if (want_tr) {
@@ -102,7 +104,7 @@ __global__ void __launch_bounds__(256) sat_attn_prepare_kernel(SatPrepParams p) 
     }
     if (!want_tr) return;   // block-uniform
     __syncthreads();
-    for (int i = threadIdx.x; i < SAT_ATT_T * SAT_ATT_D / 8; i += 256) {
+    for (int i = threadIdx.x; i < D * (SAT_ATT_T / 8); i += 256) {
         const int d = i >> 3, r0 = (i & 7) * 8;
         bf16x8 vh, vl;
 #pragma unroll
@@ -116,16 +118,37 @@ __global__ void __launch_bounds__(256) sat_attn_prepare_kernel(SatPrepParams p) 
     }
 }
 
-extern "C" int sat_attn_prepare(const void* src, long long sb, long long sh, long long sn, short* rm_hi, short* rm_lo,
-                                short* tr_hi, short* tr_lo, int B, int H, int N, int Np, int dtype, void* stream) {
-    if (B <= 0 || H <= 0 || N <= 0) { sat_set_error("sat_attn_prepare: empty shape"); return 1; }
-    if (Np < N || (Np % SAT_ATT_T) != 0) { sat_set_error("sat_attn_prepare: Np must be N rounded up to a multiple of 64"); return 1; }
-    if (dtype != 0 && dtype != 1) { sat_set_error("sat_attn_prepare: dtype must be 0 (f32) or 1 (bf16)"); return 1; }
+// one body for sat_attn_prepare (head dim 64) and sat_attn_prepare_hd; `who` names the caller in the messages
+static int sat_attn_prepare_any(const void* src, long long sb, long long sh, long long sn, short* rm_hi, short* rm_lo, short* tr_hi,
+                                short* tr_lo, int B, int H, int N, int Np, int head_dim, int dtype, void* stream, const char* who) {
+    char msg[128];
+    if (B <= 0 || H <= 0 || N <= 0) { snprintf(msg, sizeof msg, "%s: empty shape", who); sat_set_error(msg); return 1; }
+    if (Np < N || (Np % SAT_ATT_T) != 0) { snprintf(msg, sizeof msg, "%s: Np must be N rounded up to a multiple of 64", who); sat_set_error(msg); return 1; }
+    if (dtype != 0 && dtype != 1) { snprintf(msg, sizeof msg, "%s: dtype must be 0 (f32) or 1 (bf16)", who); sat_set_error(msg); return 1; }
     SatPrepParams p{src, sb, sh, sn, rm_hi, rm_lo, tr_hi, tr_lo, B, H, N, Np};
     dim3 grid(Np / SAT_ATT_T, H, B);
-    if (dtype == 0) SAT_LAUNCH(sat_attn_prepare_kernel<float>, grid, dim3(256), stream, p);
-    else SAT_LAUNCH(sat_attn_prepare_kernel<short>, grid, dim3(256), stream, p);
-    return sat_check_launch("sat_attn_prepare");
+    if (head_dim == 64) {
+        if (dtype == 0) SAT_LAUNCH((sat_attn_prepare_kernel<float, 64>), grid, dim3(256), stream, p);
+        else SAT_LAUNCH((sat_attn_prepare_kernel<short, 64>), grid, dim3(256), stream, p);
+    } else {
+        if (dtype == 0) SAT_LAUNCH((sat_attn_prepare_kernel<float, 128>), grid, dim3(256), stream, p);
+        else SAT_LAUNCH((sat_attn_prepare_kernel<short, 128>), grid, dim3(256), stream, p);
+    }
+    return sat_check_launch(who);
+}
+
+extern "C" int sat_attn_prepare(const void* src, long long sb, long long sh, long long sn, short* rm_hi, short* rm_lo,
+                                short* tr_hi, short* tr_lo, int B, int H, int N, int Np, int dtype, void* stream) {
+    return sat_attn_prepare_any(src, sb, sh, sn, rm_hi, rm_lo, tr_hi, tr_lo, B, H, N, Np, 64, dtype, stream, "sat_attn_prepare");
+}
+
+// sat_attn_prepare with the head dim as an argument: 64 is sat_attn_prepare itself (its messages included), 128 writes [B][H][Np][128] /
+// [B][H][128][Np] planes
+extern "C" int sat_attn_prepare_hd(const void* src, long long sb, long long sh, long long sn, short* rm_hi, short* rm_lo,
+                                   short* tr_hi, short* tr_lo, int B, int H, int N, int Np, int head_dim, int dtype, void* stream) {
+    if (head_dim != 64 && head_dim != 128) { sat_set_error("sat_attn_prepare_hd: head_dim must be 64 or 128"); return 1; }
+    return sat_attn_prepare_any(src, sb, sh, sn, rm_hi, rm_lo, tr_hi, tr_lo, B, H, N, Np, head_dim, dtype, stream,
+                                head_dim == 64 ? "sat_attn_prepare" : "sat_attn_prepare_hd");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -287,9 +310,10 @@ SAT_DEVICE float sat_att_sum2(uint32_t w, float acc) {
 // DOT2 (bf16 planes: NP == 1; round 5 — timed in profiles/r05_experiments/lean_ab/): P is packed to bf16 BEFORE the row sum, which then
 // runs on sat_att_sum2 over the packed words — 16 instructions per 64-key tile instead of 32 adds; the normaliser is the sum of the
 // ROUNDED probabilities (what P V multiplies): the output is normalised consistently, the LSE moves by <= 2^-9 / sqrt(keys) relative.
-template <int NP, int NKB, bool MASK, bool FIRST, bool DOT2 = false>
-SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][SAT_ATT_ROW], short (*v_lds)[SAT_ATT_D][SAT_ATT_ROW], const bf16x8 (&qf)[4][NP],
-                                  f32x16 (&oacc)[2], f32x16& negm, float& mb, float& l_run, int l31, int hi, int kperm, int nvalid) {
+// D: D / 16 k-steps in QK^T, D / 32 32-row blocks of O^T in P V.
+template <int D, int NP, int NKB, bool MASK, bool FIRST, bool DOT2>
+SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][D + 8], short (*v_lds)[D][SAT_ATT_ROW], const bf16x8 (&qf)[D / 16][NP],
+                                  f32x16 (&oacc)[D / 32], f32x16& negm, float& mb, float& l_run, int l31, int hi, int kperm, int nvalid) {
     f32x16 sacc[NKB];
     auto qk = [&]() {
         SAT_SETPRIO(1);
@@ -300,7 +324,7 @@ SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][SAT_ATT_ROW], short 
                 for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.0f;
             }
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
+            for (int s = 0; s < D / 16; ++s) {
                 bf16x8 ka[NP];
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) ka[pl] = sat_att_frag_rm(k_lds[pl], kb * 32 + kperm, 16 * s + 8 * hi);
@@ -379,7 +403,7 @@ SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][SAT_ATT_ROW], short 
             mb += d;
             l_run *= alpha;
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
+            for (int t = 0; t < D / 32; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
 #pragma unroll
@@ -401,7 +425,7 @@ SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][SAT_ATT_ROW], short 
             if (DOT2) pb[0] = pbs[DOT2 ? kb : 0][u];
             else sat_att_pack<NP>(sacc[kb], u, pb);
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
+            for (int t = 0; t < D / 32; ++t) {
                 bf16x8 va[NP];
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) va[pl] = sat_att_frag_rm(v_lds[pl], t * 32 + l31, kb * 32 + 16 * u + 8 * hi);
@@ -411,35 +435,60 @@ SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][SAT_ATT_ROW], short 
     SAT_SETPRIO(0);
 }
 
-template <typename T, int NP>
-__global__ void __launch_bounds__(256)
+// The forward at head dim D = 64 / 128, NW waves of 32 queries per workgroup.  One wave owns 32 queries, 64-key tiles go through LDS, the
+// products are swapped (S^T = K Q^T, O^T += V^T P^T) so that a softmax row is lane-local, and the tile function above does the rest.  What
+// D sets: D / 16 16-wide k-steps for Q (qf[D / 16][NP]), D / 32 32-row blocks of O^T (oacc[D / 32]), a K tile of [64][D + 8] (144 B /
+// 272 B row stride, conflict-free ds_read_b128) and a V^T tile of [D][64 + 8] per plane and buffer — 18 432 B at D = 64, 35 840 B at 128.
+// Per 64-key tile a wave issues 16 / 32 MFMAs (x3 in the two-plane mode) for the same 64 x 32 scores' worth of softmax.
+//
+// LDS / occupancy, as chosen (sat_attention_fwd instantiates exactly these five):
+//   D = 64,  NP = 1 | 2, NW = 4:  double-buffered, 36 864 B | 73 728 B per workgroup, amdgpu_waves_per_eu(3): >= 3 workgroups per CU, so
+//                   that the softmax VALU of one overlaps the MFMAs of another.
+//   D = 128, NP = 1 (bf16):  double-buffered, 71 680 B per workgroup, 256 registers per lane (amdgpu_waves_per_eu(2)): two waves per SIMD,
+//                   which the softmax of one wave needs to run under the MFMAs of another.  Two shapes: NW = 4 waves per workgroup (128
+//                   queries; two workgroups share a CU when the grid is that large) and NW = 8 (256 queries: the two waves of a SIMD
+//                   belong to ONE workgroup and share its K / V^T tiles, half the staging per MFMA) — sat_attention_fwd picks 8 when
+//                   256-query workgroups still give every CU one.
+//   D = 128, NP = 2 (fp32):  NW = 4, double-buffered as well, 143 360 B (inside the 160 KB gemm.hip relies on): ONE workgroup per CU, one
+//                   wave per SIMD (amdgpu_waves_per_eu(1)), with the whole 512-register file for qf (64) + oacc (64) + scores (32) + the
+//                   tile in flight (64).  Single-buffering would allow two workgroups per CU only below 256 registers, which this
+//                   instantiation cannot meet without spilling, and a single-buffered lone workgroup would expose every tile's
+//                   global-load latency; this is the 1e-3 parity mode, so it keeps the simple pipeline of D = 64 instead.
+// There is no backward at head dim 128: sat_attention_bwd refuses it (the two-plane dK / dV tile already needs TQ = 32 to fit LDS at D = 64).
+template <typename T, int NP, int D, int NW>
+__global__ void __launch_bounds__(64 * NW)
 #if !defined(SAT_HIPEMU)
-__attribute__((amdgpu_waves_per_eu(3)))       // >= 3 workgroups per CU so that softmax VALU of one overlaps MFMAs of another
+__attribute__((amdgpu_waves_per_eu(D == 64 ? 3 : NP == 1 ? 2 : 1)))      // the occupancy each shape's registers must leave room for (above)
 #endif
 sat_attn_fwd_kernel(SatAttnParams p) {
+    constexpr int THREADS = 64 * NW, QWG = 32 * NW;      // NW waves of 32 queries each
+    constexpr int KPARTS = D / 8;                        // 16-byte pieces per row of the K tile (the V^T tile's rows hold 8)
+    constexpr int PIECES = SAT_ATT_T * KPARTS / THREADS; // 16-byte pieces of a K / V^T tile per thread and plane
+    static_assert(D % 32 == 0, "D / 16 k-steps and D / 32 blocks of O^T");
+    static_assert(PIECES * THREADS == SAT_ATT_T * D / 8, "the workgroup's threads must tile the K / V^T pieces exactly");
     // K / V^T tiles double-buffered in LDS; tile k+1 travels through registers while tile k is consumed: one barrier per tile
-    __shared__ __attribute__((aligned(16))) short k_lds2[2][NP][SAT_ATT_T][SAT_ATT_ROW];   // [buffer][plane][key][d]
-    __shared__ __attribute__((aligned(16))) short v_lds2[2][NP][SAT_ATT_D][SAT_ATT_ROW];   // [buffer][plane][d][key]
+    __shared__ __attribute__((aligned(16))) short k_lds2[2][NP][SAT_ATT_T][D + 8];      // [buffer][plane][key][d]
+    __shared__ __attribute__((aligned(16))) short v_lds2[2][NP][D][SAT_ATT_ROW];        // [buffer][plane][d][key]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int kperm = sat_att_kperm(l31);
     const int b = blockIdx.z, h = blockIdx.y;
     const int hk = h / (p.H / p.Hkv);
-    const int qrow = blockIdx.x * 128 + wave * 32 + l31;     // < Nqp (grid covers Nqp in steps of 128 only when present)
+    const int qrow = blockIdx.x * QWG + wave * 32 + l31;     // < Nqp when q_in: Nqp is a multiple of 64, the grid covers Nq in steps of QWG
     const bool q_in = qrow < p.Nqp;
     const bool q_ok = qrow < p.Nq;
-    const bool w_ok = blockIdx.x * 128 + wave * 32 < p.Nq;   // wave-uniform: this wave owns a valid query
-    const size_t qplane = ((size_t)b * p.H + h) * (size_t)p.Nqp * SAT_ATT_D;
-    const size_t kplane = ((size_t)b * p.Hkv + hk) * (size_t)p.Nkp * SAT_ATT_D;
+    const bool w_ok = blockIdx.x * QWG + wave * 32 < p.Nq;   // wave-uniform: this wave owns a valid query
+    const size_t qplane = ((size_t)b * p.H + h) * (size_t)p.Nqp * D;
+    const size_t kplane = ((size_t)b * p.Hkv + hk) * (size_t)p.Nkp * D;
     const float sl2 = p.scale * 1.4426950408889634f;
 
-    bf16x8 qf[4][NP];   // B operand of x = K (Q c)^T: lane (q = l31, hi) holds d = 16 s + 8 hi + e, pre-scaled by c = scale * log2(e)
+    bf16x8 qf[D / 16][NP];   // B operand of x = K (Q c)^T: lane (q = l31, hi) holds d = 16 s + 8 hi + e, pre-scaled by c = scale * log2(e)
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < D / 16; ++s) {
         u32x4 w[NP];
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl) {
-            if (q_in) w[pl] = *reinterpret_cast<const u32x4*>(p.q_rm[pl] + qplane + (size_t)qrow * SAT_ATT_D + 16 * s + 8 * hi);
+            if (q_in) w[pl] = *reinterpret_cast<const u32x4*>(p.q_rm[pl] + qplane + (size_t)qrow * D + 16 * s + 8 * hi);
             else w[pl] = u32x4{0u, 0u, 0u, 0u};
         }
 #pragma unroll
@@ -460,36 +509,39 @@ sat_attn_fwd_kernel(SatAttnParams p) {
         for (int pl = 0; pl < NP; ++pl) qf[s][pl] = __builtin_bit_cast(bf16x8, w[pl]);
     }
 
-    f32x16 oacc[2], negm;
+    f32x16 oacc[D / 32], negm;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        oacc[0][r] = 0.0f;
-        oacc[1][r] = 0.0f;
+#pragma unroll
+        for (int t = 0; t < D / 32; ++t) oacc[t][r] = 0.0f;
         negm[r] = 0.0f;
     }
     float mb = 0.0f, l_run = 0.0f;      // running row max (exp2 domain) and row sum
 
-    // a 64 x 64 bf16 tile = 512 16-byte pieces = 2 per thread and plane: LDS (row, part) and the byte offsets from the tile's uniform base
-    int srow[2], spart[2];
-    unsigned kob[2], vob[2];
+    // K tile 64 x D and V^T tile D x 64 bf16 = 8 D 16-byte pieces each = PIECES per thread and plane: LDS (row, part) and the byte
+    // offsets from the tile's uniform base
+    int krow[PIECES], kpart[PIECES], vrow[PIECES], vpart[PIECES];
+    unsigned kob[PIECES], vob[PIECES];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int c = threadIdx.x + j * 256;
-        srow[j] = c >> 3;
-        spart[j] = c & 7;
-        kob[j] = (unsigned)(srow[j] * SAT_ATT_D + spart[j] * 8) * 2u;
-        vob[j] = ((unsigned)srow[j] * (unsigned)p.Nkp + (unsigned)spart[j] * 8u) * 2u;      // < 64 * Nkp * 2 bytes: Nkp < 2^24 (sat_attn_check)
+    for (int j = 0; j < PIECES; ++j) {
+        const int c = threadIdx.x + j * THREADS;
+        krow[j] = c / KPARTS;   // < 64
+        kpart[j] = c % KPARTS;
+        vrow[j] = c >> 3;       // < D
+        vpart[j] = c & 7;
+        kob[j] = (unsigned)(krow[j] * D + kpart[j] * 8) * 2u;
+        vob[j] = ((unsigned)vrow[j] * (unsigned)p.Nkp + (unsigned)vpart[j] * 8u) * 2u;      // < D * Nkp * 2 bytes: Nkp < 2^24 / 2^23 (sat_attention_fwd)
     }
     // this (batch item, kv head)'s K and V^T planes: descriptors in scalar registers (the lo planes' only exist in the two-plane mode)
     const SatBuf kbuf0 = sat_buf_make(p.k_rm[0] + kplane), vbuf0 = sat_buf_make(p.v_tr[0] + kplane);
     const SatBuf kbuf1 = sat_buf_make(p.k_rm[NP - 1] + kplane), vbuf1 = sat_buf_make(p.v_tr[NP - 1] + kplane);
-    bf16x8 kreg[NP][2], vreg[NP][2];
-    auto tile_load = [&](int k0) {
+    bf16x8 kreg[NP][PIECES], vreg[NP][PIECES];
+    auto tile_load = [&](int k0) {      // k0 + 64 <= Nkp: every 16-byte piece lies inside this (batch item, kv head)'s planes
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                kreg[pl][j] = sat_buf_load16(pl == 0 ? kbuf0 : kbuf1, kob[j], (unsigned)k0 * (SAT_ATT_D * 2));
+            for (int j = 0; j < PIECES; ++j) {
+                kreg[pl][j] = sat_buf_load16(pl == 0 ? kbuf0 : kbuf1, kob[j], (unsigned)k0 * (D * 2));
                 vreg[pl][j] = sat_buf_load16(pl == 0 ? vbuf0 : vbuf1, vob[j], (unsigned)k0 * 2u);
             }
     };
@@ -497,9 +549,9 @@ sat_attn_fwd_kernel(SatAttnParams p) {
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                *reinterpret_cast<bf16x8*>(&k_lds2[buf][pl][srow[j]][spart[j] * 8]) = kreg[pl][j];
-                *reinterpret_cast<bf16x8*>(&v_lds2[buf][pl][srow[j]][spart[j] * 8]) = vreg[pl][j];
+            for (int j = 0; j < PIECES; ++j) {
+                *reinterpret_cast<bf16x8*>(&k_lds2[buf][pl][krow[j]][kpart[j] * 8]) = kreg[pl][j];
+                *reinterpret_cast<bf16x8*>(&v_lds2[buf][pl][vrow[j]][vpart[j] * 8]) = vreg[pl][j];
             }
     };
     tile_load(0);
@@ -512,7 +564,7 @@ sat_attn_fwd_kernel(SatAttnParams p) {
             tile_store(1);
             if (2 * SAT_ATT_T < p.Nk) tile_load(2 * SAT_ATT_T);
         }
-        if (w_ok) sat_attn_fwd_tile<NP, 2, false, true, NP == 1>(k_lds2[0], v_lds2[0], qf, oacc, negm, mb, l_run, l31, hi, kperm, SAT_ATT_T);
+        if (w_ok) sat_attn_fwd_tile<D, NP, 2, false, true, NP == 1>(k_lds2[0], v_lds2[0], qf, oacc, negm, mb, l_run, l31, hi, kperm, SAT_ATT_T);
         __syncthreads();
         k0 = SAT_ATT_T;
         buf = 1;
@@ -523,18 +575,18 @@ sat_attn_fwd_kernel(SatAttnParams p) {
             tile_store(buf ^ 1);                                         // tile k+1: registers -> the other buffer
             if (k0 + 2 * SAT_ATT_T < p.Nk) tile_load(k0 + 2 * SAT_ATT_T);   // tile k+2 -> registers (lands during this tile's math)
         }
-        if (w_ok) sat_attn_fwd_tile<NP, 2, false, false, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, SAT_ATT_T);
+        if (w_ok) sat_attn_fwd_tile<D, NP, 2, false, false, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, SAT_ATT_T);
         __syncthreads();
     }
     if (k0 < p.Nk && w_ok) {
         const int rem = p.Nk - k0;
         if (k0 == 0) {            // fewer than 64 keys in all: the ragged tile is also the first
-            if (rem > 32) sat_attn_fwd_tile<NP, 2, true, true, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, rem);
-            else sat_attn_fwd_tile<NP, 1, true, true, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, rem);
+            if (rem > 32) sat_attn_fwd_tile<D, NP, 2, true, true, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, rem);
+            else sat_attn_fwd_tile<D, NP, 1, true, true, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, rem);
         } else if (rem > 32) {
-            sat_attn_fwd_tile<NP, 2, true, false, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, rem);
+            sat_attn_fwd_tile<D, NP, 2, true, false, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, rem);
         } else {
-            sat_attn_fwd_tile<NP, 1, true, false, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, rem);
+            sat_attn_fwd_tile<D, NP, 1, true, false, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, rem);
         }
     }
 
@@ -542,9 +594,9 @@ sat_attn_fwd_kernel(SatAttnParams p) {
     const float inv_l = 1.0f / l_tot;
     if (q_ok) {
         // lane (q, hi) holds d = 32 t + 8 g + 4 hi + {0..3} in registers 4 g + {0..3}: 8-byte (bf16) / 16-byte (fp32) stores
-        const long long obase = ((long long)b * p.Nq + qrow) * ((long long)p.H * SAT_ATT_D) + (long long)h * SAT_ATT_D;
+        const long long obase = ((long long)b * p.Nq + qrow) * ((long long)p.H * D) + (long long)h * D;
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+        for (int t = 0; t < D / 32; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 v = {oacc[t][4 * g] * inv_l, oacc[t][4 * g + 1] * inv_l, oacc[t][4 * g + 2] * inv_l, oacc[t][4 * g + 3] * inv_l};
@@ -1487,13 +1539,11 @@ __global__ void __launch_bounds__(256) sat_attn_rowdot_kernel(SatRowdotParams p)
 // ---------------------------------------------------------------------------------------------
 // host entry points
 // ---------------------------------------------------------------------------------------------
-#include "attention_hd128.h"
-
-// fwd_only: the forward also serves head_dim == 128 (attention_hd128.h); everything else is head dim 64
+// fwd_only: the forward also serves head_dim == 128 (sat_attn_fwd_kernel at D = 128); everything else is head dim 64
 static int sat_attn_check(int B, int H, int Hkv, int Nq, int Nk, int Nqp, int Nkp, int head_dim, int dtype, const char* who, bool fwd_only = false) {
     if (B <= 0 || H <= 0 || Hkv <= 0 || Nq <= 0 || Nk <= 0) { sat_set_error(who); return 1; }
-    if (head_dim == SAT_ATT_D2 && !fwd_only) { sat_set_error("attention: head_dim == 128 is inference-only (forward kernels; there is no backward at head dim 128)"); return 1; }
-    if (head_dim != SAT_ATT_D && head_dim != SAT_ATT_D2) { sat_set_error("attention: only head_dim == 64 (forward and backward) and 128 (forward) are implemented"); return 1; }
+    if (head_dim == 128 && !fwd_only) { sat_set_error("attention: head_dim == 128 is inference-only (forward kernels; there is no backward at head dim 128)"); return 1; }
+    if (head_dim != 64 && head_dim != 128) { sat_set_error("attention: only head_dim == 64 (forward and backward) and 128 (forward) are implemented"); return 1; }
     if (H % Hkv != 0) { sat_set_error("attention: H must be a multiple of Hkv"); return 1; }
     if (Nqp < Nq || Nkp < Nk || Nqp % SAT_ATT_T || Nkp % SAT_ATT_T) { sat_set_error("attention: padded lengths must be multiples of 64 and cover N"); return 1; }
     if (dtype < 0 || dtype > 3) { sat_set_error("attention: dtype must be 0 (f32, split planes) or 1 (bf16; forward only: 2 / 3 = bf16 with 32 / 64 queries per wave forced)"); return 1; }
@@ -1510,20 +1560,20 @@ extern "C" int sat_attention_fwd(const short* q_hi, const short* q_lo, const sho
     p.q_rm[0] = q_hi; p.q_rm[1] = q_lo; p.k_rm[0] = k_hi; p.k_rm[1] = k_lo; p.v_tr[0] = vt_hi; p.v_tr[1] = vt_lo;
     p.o = o; p.lse = lse; p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = Nq; p.Nk = Nk; p.Nqp = Nqp; p.Nkp = Nkp; p.scale = scale;
     dim3 grid(sat_cdiv(Nq, 128), H, B);
-    if (head_dim == SAT_ATT_D2) {      // one kernel per dtype: the 64-query and the short-key kernels are head dim 64 only
+    if (head_dim == 128) {      // one kernel per dtype: the 64-query and the short-key kernels are head dim 64 only
         if (dtype == 3) { sat_set_error("sat_attention_fwd: dtype 3 (64 queries per wave) exists at head_dim == 64 only"); return 1; }
         // a V^T tile is 128 rows of a transposed plane behind one 32-bit buffer offset
         if (Nkp >= (1 << 23)) { sat_set_error("attention: head_dim == 128 serves fewer than 2^23 keys"); return 1; }
         // bf16: 8 waves (256 queries) per workgroup when such workgroups still give every CU one, else 4 (profiles/attn_head_dim128/README.md)
         // (dtype 2 forces 4: A/B runs and the tests' second implementation)
         const bool w8 = dtype == 1 && (long long)sat_cdiv(Nq, 256) * H * B >= sat_cu_count();
-        if (dtype == 0) SAT_LAUNCH((sat_attn_fwd128_kernel<float, 2, 4>), grid, dim3(256), stream, p);
-        else if (w8) SAT_LAUNCH((sat_attn_fwd128_kernel<short, 1, 8>), dim3(sat_cdiv(Nq, 256), H, B), dim3(512), stream, p);
-        else SAT_LAUNCH((sat_attn_fwd128_kernel<short, 1, 4>), grid, dim3(256), stream, p);
+        if (dtype == 0) SAT_LAUNCH((sat_attn_fwd_kernel<float, 2, 128, 4>), grid, dim3(256), stream, p);
+        else if (w8) SAT_LAUNCH((sat_attn_fwd_kernel<short, 1, 128, 8>), dim3(sat_cdiv(Nq, 256), H, B), dim3(512), stream, p);
+        else SAT_LAUNCH((sat_attn_fwd_kernel<short, 1, 128, 4>), grid, dim3(256), stream, p);
         return sat_check_launch("sat_attention_fwd");
     }
     if (dtype == 0) {
-        SAT_LAUNCH((sat_attn_fwd_kernel<float, 2>), grid, dim3(256), stream, p);
+        SAT_LAUNCH((sat_attn_fwd_kernel<float, 2, 64, 4>), grid, dim3(256), stream, p);
     } else {
         // bf16: 64 queries per wave (sat_attn_fwd_q_kernel<2>) for LONG sequences whose 256-query workgroups still put >= 2 on every CU,
         // else 32 — measured (profiles/r06_experiments/attn_q64/): N = 6145 520 vs 530 us (0.357 vs 0.350 of the bf16 peak), N = 1025
@@ -1532,24 +1582,9 @@ extern "C" int sat_attention_fwd(const short* q_hi, const short* q_lo, const sho
         const long long wg64 = (long long)sat_cdiv(Nq, 256) * H * B;
         const bool q64 = dtype == 3 || (dtype == 1 && Nq >= 2048 && wg64 >= 2LL * sat_cu_count());
         if (q64) SAT_LAUNCH((sat_attn_fwd_q_kernel<2>), dim3(sat_cdiv(Nq, 256), H, B), dim3(256), stream, p);
-        else SAT_LAUNCH((sat_attn_fwd_kernel<short, 1>), grid, dim3(256), stream, p);
+        else SAT_LAUNCH((sat_attn_fwd_kernel<short, 1, 64, 4>), grid, dim3(256), stream, p);
     }
     return sat_check_launch("sat_attention_fwd");
-}
-
-// sat_attn_prepare with the head dim as an argument: 64 is sat_attn_prepare itself, 128 writes [B][H][Np][128] / [B][H][128][Np] planes
-extern "C" int sat_attn_prepare_hd(const void* src, long long sb, long long sh, long long sn, short* rm_hi, short* rm_lo,
-                                   short* tr_hi, short* tr_lo, int B, int H, int N, int Np, int head_dim, int dtype, void* stream) {
-    if (head_dim == SAT_ATT_D) return sat_attn_prepare(src, sb, sh, sn, rm_hi, rm_lo, tr_hi, tr_lo, B, H, N, Np, dtype, stream);
-    if (head_dim != SAT_ATT_D2) { sat_set_error("sat_attn_prepare_hd: head_dim must be 64 or 128"); return 1; }
-    if (B <= 0 || H <= 0 || N <= 0) { sat_set_error("sat_attn_prepare_hd: empty shape"); return 1; }
-    if (Np < N || (Np % SAT_ATT_T) != 0) { sat_set_error("sat_attn_prepare_hd: Np must be N rounded up to a multiple of 64"); return 1; }
-    if (dtype != 0 && dtype != 1) { sat_set_error("sat_attn_prepare_hd: dtype must be 0 (f32) or 1 (bf16)"); return 1; }
-    SatPrepParams p{src, sb, sh, sn, rm_hi, rm_lo, tr_hi, tr_lo, B, H, N, Np};
-    dim3 grid(Np / SAT_ATT_T, H, B);
-    if (dtype == 0) SAT_LAUNCH(sat_attn_prepare128_kernel<float>, grid, dim3(256), stream, p);
-    else SAT_LAUNCH(sat_attn_prepare128_kernel<short>, grid, dim3(256), stream, p);
-    return sat_check_launch("sat_attn_prepare_hd");
 }
 
 extern "C" int sat_attention_rowdot(const void* dout, const void* out, float* dsum, int B, int H, int Nq, int dtype,

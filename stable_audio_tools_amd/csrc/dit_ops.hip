@@ -608,6 +608,8 @@ extern "C" int sat_rope_apply(void* t, const float* cs, long long sb, long long 
 // normalised (the q and k heads of a fused (B, N, 3*H*64) projection: nh = 2H; q alone: nh = H; the k half of (B, M, 2*Hkv*64): nh = Hkv),
 // heads j < hq take the q tables, the others the k tables.  16 lanes per row, 4 columns per lane (16-byte fp32 / 8-byte bf16 accesses),
 // the row statistics are 16-lane butterflies.  mode 1 = "ln" (fp32 mean / biased variance, eps, affine), 2 = "l2" (x / max(|x|, 1e-12)).
+// The forward also runs at head dim 128 (sat_qk_norm_fwd_hd; inference only, there is no backward at that head dim): read 64 as 128
+// above, 32 lanes per row, 8 rows per workgroup, 32-lane butterflies; the rotary then covers the first 64 dims and its table is (Ntab, 32, 2).
 // ------------------------------------------------------------------------------------------------
 struct SatQkNormParams {
     const void* x;        // raw projection
@@ -649,37 +651,43 @@ template <> struct SatRow4<short> {
         *reinterpret_cast<u32x2_t*>((short*)p + i) = u;
     }
 };
-SAT_DEVICE float sat_group16_sum(float v) {
-    for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+// sum over the row's group of LANES consecutive lanes, in every lane of the group
+template <int LANES>
+SAT_DEVICE float sat_group_sum(float v) {
+    for (int m = LANES / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m);
     return v;
 }
-// partial rotary on the lane's four columns c .. c+3 (first 32 dims, NeoX pairs (d, d + 16)); pv = the partner columns c ^ 16, which
-// live 4 lanes away in the row's 16-lane group.  sign +1: forward, -1: transpose (backward).
+// partial rotary on the lane's four columns c .. c+3 (first 2 HALF dims, NeoX pairs (d, d + HALF); HALF = 16 at head dim 64, 32 at 128:
+// RotaryEmbedding(max(dim_heads // 2, 32))); pv = the partner columns c ^ HALF, which live HALF / 4 lanes away in the row's group; the
+// table is (Ntab, HALF, 2).  sign +1: forward, -1: transpose (backward).
+template <int HALF>
 SAT_DEVICE f32x4 sat_qk_rotate(f32x4 v, f32x4 pv, const float* cs, long long tab_row, int c, float sign) {
-    const float* t = cs + (tab_row * 16 + (c & 15)) * 2;
+    const float* t = cs + (tab_row * HALF + (c & (HALF - 1))) * 2;
     const f32x4 cs0 = *reinterpret_cast<const f32x4*>(t), cs1 = *reinterpret_cast<const f32x4*>(t + 4);
     const float co[4] = {cs0[0], cs0[2], cs1[0], cs1[2]}, si[4] = {cs0[1], cs0[3], cs1[1], cs1[3]};
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (c < 16) ? v[e] * co[e] - pv[e] * (sign * si[e]) : v[e] * co[e] + pv[e] * (sign * si[e]);
+    for (int e = 0; e < 4; ++e) o[e] = (c < HALF) ? v[e] * co[e] - pv[e] * (sign * si[e]) : v[e] * co[e] + pv[e] * (sign * si[e]);
     return o;
 }
 
-template <typename T>
+// forward at head dim D = 64 / 128: D / 4 lanes per row, 1024 / D rows per workgroup
+template <typename T, int D>
 __global__ void __launch_bounds__(256) sat_qk_norm_fwd_kernel(SatQkNormParams p) {
-    const int c = (threadIdx.x & 15) * 4;
-    const long long row = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (row >= p.rows) return;            // a whole 16-lane group leaves together: the butterflies below stay inside a group
+    constexpr int LANES = D / 4, HALF = D / 4;      // lanes per row; rotary half (the two are equal by coincidence of 4 columns per lane)
+    const int c = (threadIdx.x & (LANES - 1)) * 4;
+    const long long row = (long long)blockIdx.x * (256 / LANES) + threadIdx.x / LANES;
+    if (row >= p.rows) return;            // a whole LANES-lane group leaves together: the butterflies below stay inside a group
     const long long tok = row / p.nh;
     const int j = (int)(row - tok * p.nh);
-    f32x4 v = SatRow4<T>::ld(p.x, tok * p.xs + j * 64 + c);
+    f32x4 v = SatRow4<T>::ld(p.x, tok * p.xs + j * D + c);
     float mean = 0.f, rs;
     if (p.mode == 1) {
-        mean = sat_group16_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
+        mean = sat_group_sum<LANES>((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / D);
         v -= mean;
     }
-    const float ss = sat_group16_sum((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
-    rs = (p.mode == 1) ? 1.0f / sqrtf(ss * (1.0f / 64.0f) + p.eps) : 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+    const float ss = sat_group_sum<LANES>((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
+    rs = (p.mode == 1) ? 1.0f / sqrtf(ss * (1.0f / D) + p.eps) : 1.0f / fmaxf(sqrtf(ss), 1e-12f);
     v *= rs;
     if (p.mode == 1) {
         const float* g = j < p.hq ? p.gq : p.gk;
@@ -689,10 +697,10 @@ __global__ void __launch_bounds__(256) sat_qk_norm_fwd_kernel(SatQkNormParams p)
     if (p.cs) {
         f32x4 pv;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) pv[e] = __shfl_xor(v[e], 4);
-        if (c < 32) v = sat_qk_rotate(v, pv, p.cs, p.tab_off + tok % p.ntok, c, 1.0f);
+        for (int e = 0; e < 4; ++e) pv[e] = __shfl_xor(v[e], HALF / 4);
+        if (c < 2 * HALF) v = sat_qk_rotate<HALF>(v, pv, p.cs, p.tab_off + tok % p.ntok, c, 1.0f);
     }
-    SatRow4<T>::st(p.y, tok * p.ys + j * 64 + c, v);
+    SatRow4<T>::st(p.y, tok * p.ys + j * D + c, v);
     if (p.stat && c == 0) {
         p.stat[row] = (p.mode == 1) ? mean : rs;
         if (p.mode == 1) p.stat[p.rows + row] = rs;
@@ -721,7 +729,7 @@ __global__ void __launch_bounds__(256) sat_qk_norm_bwd_kernel(SatQkNormParams p)
             f32x4 pg;
 #pragma unroll
             for (int e = 0; e < 4; ++e) pg[e] = __shfl_xor(g[e], 4);
-            if (c < 32) g = sat_qk_rotate(g, pg, p.cs, p.tab_off + tok % p.ntok, c, -1.0f);
+            if (c < 32) g = sat_qk_rotate<16>(g, pg, p.cs, p.tab_off + tok % p.ntok, c, -1.0f);
         }
         f32x4 xh = SatRow4<T>::ld(p.x, tok * p.xs + j * 64 + c);
         f32x4 dx;
@@ -734,13 +742,13 @@ __global__ void __launch_bounds__(256) sat_qk_norm_bwd_kernel(SatQkNormParams p)
                 else { acc[2] += g * xh; acc[3] += g; }
             }
             g *= *reinterpret_cast<const f32x4*>((isq ? p.gq : p.gk) + c);
-            const float s1 = sat_group16_sum((g[0] + g[1]) + (g[2] + g[3])) * (1.0f / 64.0f);
-            const float s2 = sat_group16_sum((g[0] * xh[0] + g[1] * xh[1]) + (g[2] * xh[2] + g[3] * xh[3])) * (1.0f / 64.0f);
+            const float s1 = sat_group_sum<16>((g[0] + g[1]) + (g[2] + g[3])) * (1.0f / 64.0f);
+            const float s2 = sat_group_sum<16>((g[0] * xh[0] + g[1] * xh[1]) + (g[2] * xh[2] + g[3] * xh[3])) * (1.0f / 64.0f);
             dx = (g - s1 - xh * s2) * rs;
         } else {
             const float inv = p.stat[rc];
             xh *= inv;
-            const float s2 = sat_group16_sum((g[0] * xh[0] + g[1] * xh[1]) + (g[2] * xh[2] + g[3] * xh[3]));
+            const float s2 = sat_group_sum<16>((g[0] * xh[0] + g[1] * xh[1]) + (g[2] * xh[2] + g[3] * xh[3]));
             dx = (g - xh * s2) * inv;
         }
         if (ok) SatRow4<T>::st(p.dy, tok * p.ys + j * 64 + c, dx);
@@ -767,7 +775,12 @@ __global__ void __launch_bounds__(256) sat_qk_norm_bwd_kernel(SatQkNormParams p)
 
 #define SAT_QKN_BWD_ITERS 8
 static int sat_qk_norm_check(const SatQkNormParams& p, int tokens, int dtype, const void* act0, const void* act1, bool need_beta, const char* who) {
-    if (tokens <= 0 || p.ntok <= 0 || tokens % p.ntok != 0 || p.nh <= 0 || p.hq < 0 || p.hq > p.nh) { sat_set_error(who); return 1; }
+    if (tokens <= 0 || p.ntok <= 0 || tokens % p.ntok != 0 || p.nh <= 0 || p.hq < 0 || p.hq > p.nh) {
+        char msg[64];
+        snprintf(msg, sizeof msg, "%s: bad shape", who);
+        sat_set_error(msg);
+        return 1;
+    }
     if (dtype != 0 && dtype != 1) { sat_set_error("sat_qk_norm: dtype must be 0 (f32) or 1 (bf16)"); return 1; }
     if (p.mode != 1 && p.mode != 2) { sat_set_error("sat_qk_norm: mode must be 1 (ln) or 2 (l2)"); return 1; }
     const int al = dtype == 0 ? 15 : 7;
@@ -782,87 +795,47 @@ static int sat_qk_norm_check(const SatQkNormParams& p, int tokens, int dtype, co
     return 0;
 }
 
+// one body for sat_qk_norm_fwd (head dim 64) and sat_qk_norm_fwd_hd; `who` names the caller in the messages
+static int sat_qk_norm_fwd_any(const void* x, long long xs, void* y, long long ys, const float* q_gamma, const float* q_beta,
+                               const float* k_gamma, const float* k_beta, const float* cs, int tab_off, float* stat, int tokens, int ntok,
+                               int nh, int hq, int mode, float eps, int head_dim, int dtype, void* stream, const char* who) {
+    SatQkNormParams p{};
+    p.x = x; p.y = y; p.gq = q_gamma; p.bq = q_beta; p.gk = k_gamma; p.bk = k_beta; p.cs = cs; p.stat = stat;
+    p.xs = xs; p.ys = ys; p.ntok = ntok; p.nh = nh; p.hq = hq; p.tab_off = tab_off; p.mode = mode; p.eps = eps;
+    if (sat_qk_norm_check(p, tokens, dtype, x, y, true, who)) return 1;
+    if (xs < (long long)nh * head_dim || ys < (long long)nh * head_dim) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "%s: rows must hold nh * %d elements", who, head_dim);
+        sat_set_error(msg);
+        return 1;
+    }
+    p.rows = (long long)tokens * nh;
+    dim3 grid((unsigned)sat_cdivll(p.rows, 1024 / head_dim));
+    if (head_dim == 64) {
+        if (dtype == 0) SAT_LAUNCH((sat_qk_norm_fwd_kernel<float, 64>), grid, dim3(256), stream, p);
+        else SAT_LAUNCH((sat_qk_norm_fwd_kernel<short, 64>), grid, dim3(256), stream, p);
+    } else {
+        if (dtype == 0) SAT_LAUNCH((sat_qk_norm_fwd_kernel<float, 128>), grid, dim3(256), stream, p);
+        else SAT_LAUNCH((sat_qk_norm_fwd_kernel<short, 128>), grid, dim3(256), stream, p);
+    }
+    return sat_check_launch(who);
+}
+
 // y = rotary(norm(x)) on the first nh heads of every token; stat fp32 ("ln": (2, tokens * nh), "l2": (tokens * nh)) or NULL (no backward).  cs (tab_off + ntok, 16, 2).
 extern "C" int sat_qk_norm_fwd(const void* x, long long xs, void* y, long long ys, const float* q_gamma, const float* q_beta,
                                const float* k_gamma, const float* k_beta, const float* cs, int tab_off, float* stat, int tokens, int ntok,
                                int nh, int hq, int mode, float eps, int dtype, void* stream) {
-    SatQkNormParams p{};
-    p.x = x; p.y = y; p.gq = q_gamma; p.bq = q_beta; p.gk = k_gamma; p.bk = k_beta; p.cs = cs; p.stat = stat;
-    p.xs = xs; p.ys = ys; p.ntok = ntok; p.nh = nh; p.hq = hq; p.tab_off = tab_off; p.mode = mode; p.eps = eps;
-    if (sat_qk_norm_check(p, tokens, dtype, x, y, true, "sat_qk_norm_fwd: bad shape")) return 1;
-    p.rows = (long long)tokens * nh;
-    dim3 grid((unsigned)sat_cdivll(p.rows, 16));
-    if (dtype == 0) SAT_LAUNCH(sat_qk_norm_fwd_kernel<float>, grid, dim3(256), stream, p);
-    else SAT_LAUNCH(sat_qk_norm_fwd_kernel<short>, grid, dim3(256), stream, p);
-    return sat_check_launch("sat_qk_norm_fwd");
+    return sat_qk_norm_fwd_any(x, xs, y, ys, q_gamma, q_beta, k_gamma, k_beta, cs, tab_off, stat, tokens, ntok, nh, hq, mode, eps, 64, dtype, stream, "sat_qk_norm_fwd");
 }
 
-// ------------------------------------------------------------------------------------------------
-// The same forward at head dim 128 (inference only: there is no backward at that head dim).  A row is 128 values: 32 lanes per row, 4
-// columns per lane, 8 rows per workgroup, the row statistics are 32-lane butterflies.  The rotary covers the first 64 dims
-// (RotaryEmbedding(max(dim_heads // 2, 32)): half = 32, NeoX pairs (d, d + 32)), so the partner columns c ^ 32 live 8 lanes away and
-// the table is (Ntab, 32, 2).
-// ------------------------------------------------------------------------------------------------
-SAT_DEVICE float sat_group32_sum(float v) {
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-template <typename T>
-__global__ void __launch_bounds__(256) sat_qk_norm128_fwd_kernel(SatQkNormParams p) {
-    const int c = (threadIdx.x & 31) * 4;
-    const long long row = (long long)blockIdx.x * 8 + (threadIdx.x >> 5);
-    if (row >= p.rows) return;            // a whole 32-lane group leaves together: the butterflies below stay inside a group
-    const long long tok = row / p.nh;
-    const int j = (int)(row - tok * p.nh);
-    f32x4 v = SatRow4<T>::ld(p.x, tok * p.xs + j * 128 + c);
-    float mean = 0.f, rs;
-    if (p.mode == 1) {
-        mean = sat_group32_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 128.0f);
-        v -= mean;
-    }
-    const float ss = sat_group32_sum((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
-    rs = (p.mode == 1) ? 1.0f / sqrtf(ss * (1.0f / 128.0f) + p.eps) : 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-    v *= rs;
-    if (p.mode == 1) {
-        const float* g = j < p.hq ? p.gq : p.gk;
-        const float* b = j < p.hq ? p.bq : p.bk;
-        v = v * *reinterpret_cast<const f32x4*>(g + c) + *reinterpret_cast<const f32x4*>(b + c);
-    }
-    if (p.cs) {
-        f32x4 pv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pv[e] = __shfl_xor(v[e], 8);
-        if (c < 64) {
-            const float* t = p.cs + ((p.tab_off + tok % p.ntok) * 32 + (c & 31)) * 2;
-            const f32x4 cs0 = *reinterpret_cast<const f32x4*>(t), cs1 = *reinterpret_cast<const f32x4*>(t + 4);
-            const float co[4] = {cs0[0], cs0[2], cs1[0], cs1[2]}, si[4] = {cs0[1], cs0[3], cs1[1], cs1[3]};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (c < 32) ? v[e] * co[e] - pv[e] * si[e] : v[e] * co[e] + pv[e] * si[e];
-        }
-    }
-    SatRow4<T>::st(p.y, tok * p.ys + j * 128 + c, v);
-    if (p.stat && c == 0) {
-        p.stat[row] = (p.mode == 1) ? mean : rs;
-        if (p.mode == 1) p.stat[p.rows + row] = rs;
-    }
-}
-
-// sat_qk_norm_fwd with the head dim as an argument: 64 is sat_qk_norm_fwd itself; 128: rows of 128 values, tables (128,), cs (tab_off + ntok, 32, 2)
+// sat_qk_norm_fwd with the head dim as an argument: 64 is sat_qk_norm_fwd itself (its messages included); 128 (inference only: there is no
+// backward at that head dim): rows of 128 values, tables (128,), cs (tab_off + ntok, 32, 2)
 extern "C" int sat_qk_norm_fwd_hd(const void* x, long long xs, void* y, long long ys, const float* q_gamma, const float* q_beta,
                                   const float* k_gamma, const float* k_beta, const float* cs, int tab_off, float* stat, int tokens, int ntok,
                                   int nh, int hq, int mode, float eps, int head_dim, int dtype, void* stream) {
-    if (head_dim == 64) return sat_qk_norm_fwd(x, xs, y, ys, q_gamma, q_beta, k_gamma, k_beta, cs, tab_off, stat, tokens, ntok, nh, hq, mode, eps, dtype, stream);
-    if (head_dim != 128) { sat_set_error("sat_qk_norm_fwd_hd: head_dim must be 64 or 128"); return 1; }
-    SatQkNormParams p{};
-    p.x = x; p.y = y; p.gq = q_gamma; p.bq = q_beta; p.gk = k_gamma; p.bk = k_beta; p.cs = cs; p.stat = stat;
-    p.xs = xs; p.ys = ys; p.ntok = ntok; p.nh = nh; p.hq = hq; p.tab_off = tab_off; p.mode = mode; p.eps = eps;
-    if (sat_qk_norm_check(p, tokens, dtype, x, y, true, "sat_qk_norm_fwd_hd: bad shape")) return 1;
-    if (xs < (long long)nh * 128 || ys < (long long)nh * 128) { sat_set_error("sat_qk_norm_fwd_hd: rows must hold nh * 128 elements"); return 1; }
-    p.rows = (long long)tokens * nh;
-    dim3 grid((unsigned)sat_cdivll(p.rows, 8));
-    if (dtype == 0) SAT_LAUNCH(sat_qk_norm128_fwd_kernel<float>, grid, dim3(256), stream, p);
-    else SAT_LAUNCH(sat_qk_norm128_fwd_kernel<short>, grid, dim3(256), stream, p);
-    return sat_check_launch("sat_qk_norm_fwd_hd");
+    if (head_dim != 64 && head_dim != 128) { sat_set_error("sat_qk_norm_fwd_hd: head_dim must be 64 or 128"); return 1; }
+    return sat_qk_norm_fwd_any(x, xs, y, ys, q_gamma, q_beta, k_gamma, k_beta, cs, tab_off, stat, tokens, ntok, nh, hq, mode, eps, head_dim, dtype, stream,
+                               head_dim == 64 ? "sat_qk_norm_fwd" : "sat_qk_norm_fwd_hd");
 }
 
 extern "C" int sat_qk_norm_bwd_nblocks(long long rows) { return (int)sat_cdivll(rows, 16 * SAT_QKN_BWD_ITERS); }
@@ -875,7 +848,7 @@ extern "C" int sat_qk_norm_bwd(void* dy, long long ys, const void* x, long long 
     SatQkNormParams p{};
     p.x = x; p.dy = dy; p.gq = q_gamma; p.gk = k_gamma; p.cs = cs; p.stat = const_cast<float*>(stat); p.part = part;
     p.xs = xs; p.ys = ys; p.ntok = ntok; p.nh = nh; p.hq = hq; p.tab_off = tab_off; p.mode = mode;
-    if (sat_qk_norm_check(p, tokens, dtype, x, dy, false, "sat_qk_norm_bwd: bad shape")) return 1;
+    if (sat_qk_norm_check(p, tokens, dtype, x, dy, false, "sat_qk_norm_bwd")) return 1;
     if (!stat || (mode == 1 && !part)) { sat_set_error("sat_qk_norm_bwd: statistics / partial-sum buffer missing"); return 1; }
     p.rows = (long long)tokens * nh;
     p.iters = SAT_QKN_BWD_ITERS;

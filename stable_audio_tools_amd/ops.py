@@ -1035,12 +1035,8 @@ class SatOps:
             return torch.empty(shape, dtype=torch.int16, device=t.device) if want else None
         rm_hi, rm_lo = alloc((b, h, npad, d), row_major), alloc((b, h, npad, d), row_major and split)
         tr_hi, tr_lo = alloc((b, h, d, npad), transposed), alloc((b, h, d, npad), transposed and split)
-        if d == 64:
-            self._chk(self.lib.sat_attn_prepare(_ptr(t), t.stride(0), t.stride(1), t.stride(2), _ptr(rm_hi), _ptr(rm_lo),
-                                                _ptr(tr_hi), _ptr(tr_lo), b, h, n, npad, dt, self._stream(t)))
-        else:
-            self._chk(self.lib.sat_attn_prepare_hd(_ptr(t), t.stride(0), t.stride(1), t.stride(2), _ptr(rm_hi), _ptr(rm_lo),
-                                                   _ptr(tr_hi), _ptr(tr_lo), b, h, n, npad, d, dt, self._stream(t)))
+        self._chk(self.lib.sat_attn_prepare_hd(_ptr(t), t.stride(0), t.stride(1), t.stride(2), _ptr(rm_hi), _ptr(rm_lo),
+                                               _ptr(tr_hi), _ptr(tr_lo), b, h, n, npad, d, dt, self._stream(t)))
         return {"rm": (rm_hi, rm_lo), "tr": (tr_hi, tr_lo), "n": n, "np": npad, "dt": dt, "d": d}
 
     def attention(self, q, k, v, scale, need_lse=False, return_planes=False):
@@ -1206,7 +1202,7 @@ class SatOps:
         return t
 
     QK_NORM_MODES = {"ln": 1, "l2": 2}
-    ATTN_HEAD_DIMS = (64, 128)      # 128: the inference kernels only (csrc/attention_hd128.h, sat_qk_norm_fwd_hd)
+    ATTN_HEAD_DIMS = (64, 128)      # 128: the inference kernels only (sat_attn_fwd_kernel at D = 128 in csrc/attention.hip, sat_qk_norm_fwd_hd)
 
     def _qk_tables(self, mode, tables, nh, hq, d=64):
         """(mode code, [q gamma, q beta, k gamma, k beta]) for the qk-norm kernels: fp32 (d,) tensors for "ln", Nones for "l2"."""
@@ -1238,7 +1234,7 @@ class SatOps:
         return head_dim
 
     def qk_norm(self, x, nh, hq, mode, tables=None, cs=None, eps=1e-6, out=None, save_stats=False, head_dim=None):
-        """Per-head q / k normalisation + rotary (sat_qk_norm_fwd; sat_qk_norm_fwd_hd at head dim 128, which is inference-only: read 64 as
+        """Per-head q / k normalisation + rotary (sat_qk_norm_fwd_hd: sat_qk_norm_fwd at head dim 64; head dim 128 is inference-only: read 64 as
         the head dim below — head_dim, or what the tables / the rotary table say).  x: (B, N, C) with C >= nh*64, last dim contiguous: the first nh heads
         of every token are normalised ("ln": LayerNorm over the 64 head dims with tables = (q gamma, q beta, k gamma, k beta), heads < hq
         take the q pair; "l2": x / max(|x|, 1e-12)), then rotated with cs ((>= N, 16, 2) table or None), and written to `out` (same
@@ -1257,12 +1253,8 @@ class SatOps:
             self._f32(cs)
         stat = torch.empty(2 if code == 1 else 1, b * n * nh, dtype=torch.float32, device=x.device) if save_stats else None
         tab_off = (cs.shape[0] - n) if cs is not None else 0
-        if d == 64:
-            self._chk(self.lib.sat_qk_norm_fwd(_ptr(x), x.stride(1), _ptr(out), out.stride(1), _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk), _ptr(cs),
-                                               tab_off, _ptr(stat), b * n, n, nh, hq, code, float(eps), dt, self._stream(x)))
-        else:
-            self._chk(self.lib.sat_qk_norm_fwd_hd(_ptr(x), x.stride(1), _ptr(out), out.stride(1), _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk),
-                                                  _ptr(cs), tab_off, _ptr(stat), b * n, n, nh, hq, code, float(eps), d, dt, self._stream(x)))
+        self._chk(self.lib.sat_qk_norm_fwd_hd(_ptr(x), x.stride(1), _ptr(out), out.stride(1), _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk),
+                                              _ptr(cs), tab_off, _ptr(stat), b * n, n, nh, hq, code, float(eps), d, dt, self._stream(x)))
         return (out, stat) if save_stats else out
 
     def qk_norm_bwd_(self, dy, x, stat, nh, hq, mode, tables=None, cs=None):

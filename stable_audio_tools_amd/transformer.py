@@ -532,7 +532,7 @@ class Attention(nn.Module):
 
     def _forward_hd128(self, x, kv_input, rotary_pos_emb, res, norm):
         """Head dim 128 (inference only; fp32 and bf16): projection through the Linear, then the standalone norm + rotary kernel
-        (sat_qk_norm_fwd_hd) or the in-place rotary, then plane preparation and the forward kernel of csrc/attention_hd128.h
+        (sat_qk_norm_fwd_hd) or the in-place rotary, then plane preparation and the forward kernel of csrc/attention.hip at D = 128
         (ops.attention), then to_out with the residual epilogue.  The projection-epilogue fusion of the head dim 64 bf16 path
         (gemm_heads_bf16) is not built at 128."""
         if torch.is_grad_enabled():

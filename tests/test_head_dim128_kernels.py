@@ -1,4 +1,4 @@
-"""Kernel-level tests of the head dim 128 inference path (csrc/attention_hd128.h, sat_qk_norm_fwd_hd in csrc/dit_ops.hip): the forward
+"""Kernel-level tests of the head dim 128 inference path (the D = 128 instantiations of sat_attn_fwd_kernel / sat_attn_prepare_kernel in csrc/attention.hip, sat_qk_norm_fwd_hd in csrc/dit_ops.hip): the forward
 attention in fp32 (two bf16 planes) and bf16, the plane preparation, the 128-wide q / k normalisation with its rotary, and the argument
 validation of the two new entry points.  CPU: the simulator build of the same sources; `-m gpu`: the gfx950 library.
 
