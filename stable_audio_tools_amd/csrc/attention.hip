@@ -474,9 +474,8 @@ sat_attn_fwd_kernel(SatAttnParams p) {
     const int kperm = sat_att_kperm(l31);
     const int b = blockIdx.z, h = blockIdx.y;
     const int hk = h / (p.H / p.Hkv);
-    const int qrow = blockIdx.x * QWG + wave * 32 + l31;     // < Nqp when q_in: Nqp is a multiple of 64, the grid covers Nq in steps of QWG
-    const bool q_in = qrow < p.Nqp;
-    const bool q_ok = qrow < p.Nq;
+    const int qrow = blockIdx.x * QWG + wave * 32 + l31;     // may pass Nqp (a multiple of 64): the grid covers Nq in steps of QWG
+    const bool q_ok = qrow < p.Nq;      // (< Nqp: inside the plane)
     const bool w_ok = blockIdx.x * QWG + wave * 32 < p.Nq;   // wave-uniform: this wave owns a valid query
     const size_t qplane = ((size_t)b * p.H + h) * (size_t)p.Nqp * D;
     const size_t kplane = ((size_t)b * p.Hkv + hk) * (size_t)p.Nkp * D;
@@ -488,7 +487,10 @@ sat_attn_fwd_kernel(SatAttnParams p) {
         u32x4 w[NP];
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl) {
-            if (q_in) w[pl] = *reinterpret_cast<const u32x4*>(p.q_rm[pl] + qplane + (size_t)qrow * D + 16 * s + 8 * hi);
+            // rows [Nq, Nqp) are taken as zero, not read: a padded row shares its wave with valid ones, and the stale-max branch of
+            // sat_attn_fwd_tile is wave-wide — what a plane holds past Nq (the no-grad path's persistent planes keep an earlier, longer
+            // call's rows there) must not decide whether the valid rows rescale
+            if (q_ok) w[pl] = *reinterpret_cast<const u32x4*>(p.q_rm[pl] + qplane + (size_t)qrow * D + 16 * s + 8 * hi);
             else w[pl] = u32x4{0u, 0u, 0u, 0u};
         }
 #pragma unroll
@@ -750,7 +752,8 @@ sat_attn_fwd_q_kernel(SatAttnParams p) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             u32x4 w = u32x4{0u, 0u, 0u, 0u};
-            if (qrow < p.Nqp) w = *reinterpret_cast<const u32x4*>(p.q_rm[0] + qplane + (size_t)qrow * SAT_ATT_D + 16 * s + 8 * hi);
+            // rows [Nq, Nqp) are taken as zero, not read (as sat_attn_fwd_kernel: the stale-max branch is wave-wide)
+            if (qrow < p.Nq) w = *reinterpret_cast<const u32x4*>(p.q_rm[0] + qplane + (size_t)qrow * SAT_ATT_D + 16 * s + 8 * hi);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float e0 = __builtin_bit_cast(float, w[j] << 16), e1 = __builtin_bit_cast(float, w[j] & 0xffff0000u);

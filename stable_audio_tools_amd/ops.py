@@ -1458,8 +1458,11 @@ class SatOps:
 
     def _head_planes(self, nb, heads, ntok, sec0, nsec, reuse, device):
         """The q / k / v_tr planes that sections sec0 .. sec0+nsec-1 of an attention input projection write: dict(n=, np=, q=, k=
-        (nb,H,Np,64), v_tr= (nb,H,64,Np)), zero-filled.  With `reuse` they are persistent (the no-grad path): rows / columns past the
-        sequence length are never written by the projection epilogue, so one memset at first use keeps them zero for every later call."""
+        (nb,H,Np,64), v_tr= (nb,H,64,Np)), zero-filled.  With `reuse` they are persistent (the no-grad path), kept by PADDED shape: rows /
+        columns past the sequence length are never written by the projection epilogue, so they hold zeros from the one memset at first use
+        or what a longer sequence of the same padded length left there — finite either way.  The forward kernels read neither (padded
+        query rows are taken as zero, padded keys are masked by index and meet P = 0: tests/test_attention_fp64.py pins it bit for bit);
+        the backward kernels do need zero padding and only ever see sat_attn_prepare output."""
         npad = (ntok + 63) // 64 * 64
         out = {"n": ntok, "np": npad}
         for i, (name, shape) in enumerate((("q", (nb, heads, npad, 64)), ("k", (nb, heads, npad, 64)), ("v_tr", (nb, heads, 64, npad)))):
