@@ -384,6 +384,17 @@ int sat_attn_prepare_hd(const void* src, long long sb, long long sh, long long s
 int sat_attention_fwd(const short* q_hi, const short* q_lo, const short* k_hi, const short* k_lo, const short* vt_hi,
                       const short* vt_lo, void* o, float* lse, int B, int H, int Hkv, int Nq, int Nk, int Nqp, int Nkp,
                       int head_dim, float scale, int dtype, void* stream);
+/* sat_attention_fwd for SELF-attention under a sliding window — flash-attn's window_size = (left, right), what the reference's
+ * ContinuousTransformer(sliding_window=[left, right]) hands to every layer (transformer.py:436, :845): query i sees key j iff
+ * (left < 0 or j >= i - left) and (right < 0 or j <= i + right); -1 = unbounded on that side; the diagonal is always visible.
+ * Inference only (no windowed backward).  head_dim 64 or 128, dtype 0 / 1 / 2 (2 = 1 here).  A workgroup stages only the key tiles
+ * that meet its queries' band, a wave does math only on those that meet its own.  Errors: Nq != Nk (no window on cross-attention), a
+ * side < -1, dtype 3 (the 64-query kernel, the 8-wave head dim 128 shape and the short-key kernels have no windowed variant: a windowed
+ * call always takes the 4-wave 32-query kernel).  A side that is -1 or >= N - 1 is unbounded; with both unbounded the call launches
+ * exactly what sat_attention_fwd launches. */
+int sat_attention_fwd_window(const short* q_hi, const short* q_lo, const short* k_hi, const short* k_lo, const short* vt_hi,
+                             const short* vt_lo, void* o, float* lse, int B, int H, int Hkv, int Nq, int Nk, int Nqp, int Nkp,
+                             int head_dim, float scale, int dtype, void* stream, int window_left, int window_right);
 /* dsum[b][h][q] = sum_d dout[b][q][h*64+d] * out[b][q][h*64+d]   (the softmax-gradient row term) */
 int sat_attention_rowdot(const void* dout, const void* out, float* dsum, int B, int H, int Nq, int dtype, void* stream);
 /* backward (autograd of the above): planes[16] = {q_rm, k_rm, v_rm, k_tr, q_tr, dout_rm, dout_tr, unused} x {hi, lo};

@@ -102,6 +102,7 @@ SIGNATURES = {
     "sat_attn_prepare": (_I, [_P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sat_attn_prepare_hd": (_I, [_P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sat_attention_fwd": (_I, [_P] * 8 + [_I] * 8 + [_F, _I, _P]),
+    "sat_attention_fwd_window": (_I, [_P] * 8 + [_I] * 8 + [_F, _I, _P, _I, _I]),
     "sat_attention_rowdot": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "sat_attention_bwd": (_I, [_P] * 6 + [_I] * 8 + [_F, _I, _P]),
     # edge_conv.hip

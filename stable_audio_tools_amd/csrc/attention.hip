@@ -236,6 +236,11 @@ struct SatAttnParams {
     void* dq;               // bwd out (B, H, Nq, 64)
     void* dk;               // bwd out (B, Hkv, Nk, 64)
     void* dv;
+    // sliding window of the windowed forward (sat_attention_fwd_window): -1 = unbounded on that side.  The two were appended after
+    // `scale` first; they stand here because room behind `scale` lets hipcc merge the kernarg loads of the integers below into one
+    // wider load, which renumbers the registers of every kernel that takes this struct — here only the offsets of B .. scale move
+    // (profiles/attn_sliding_window/README.md)
+    int window_left, window_right;
     int B, H, Hkv, Nq, Nk, Nqp, Nkp;
     float scale;
 };
@@ -278,6 +283,11 @@ SAT_DEVICE float sat_att_halfmax(float x) {
     return fmaxf(__builtin_bit_cast(float, r[0]), __builtin_bit_cast(float, r[1]));
 #endif
 }
+// The same over a plain lane exchange.  hipcc folds the two results of sat_att_halfmax's swap of a register with itself into the first
+// one, which holds the LOWER half's value in every lane (attention.hip's assembly: the v_max of the pair is gone).  The dense kernels
+// only need both halves of a row to agree on one reference point and keep that instruction stream; the windowed bodies need the true
+// maximum — a half with no visible key carries SAT_ATT_NOMAX — and take this one.
+SAT_DEVICE float sat_att_halfmax_x(float x) { return fmaxf(x, __shfl_xor(x, 32)); }
 // Round 4 — the forward kernel's instruction diet (profiles/EXPERIMENTS.md: the SQ counters put the kernel's time in the SIMD's issue
 // slots, not in one pipe; what was measured to help is listed here, what was measured NOT to help is in EXPERIMENTS.md):
 //   * Q is pre-scaled by scale * log2(e) once per launch (bf16 mode: one more bf16 rounding of Q; fp32 mode: hi + lo are recombined,
@@ -311,7 +321,8 @@ SAT_DEVICE float sat_att_sum2(uint32_t w, float acc) {
 // runs on sat_att_sum2 over the packed words — 16 instructions per 64-key tile instead of 32 adds; the normaliser is the sum of the
 // ROUNDED probabilities (what P V multiplies): the output is normalised consistently, the LSE moves by <= 2^-9 / sqrt(keys) relative.
 // D: D / 16 k-steps in QK^T, D / 32 32-row blocks of O^T in P V.
-template <int D, int NP, int NKB, bool MASK, bool FIRST, bool DOT2>
+// XMAX: the row max over sat_att_halfmax_x (the windowed kernel's full tiles)
+template <int D, int NP, int NKB, bool MASK, bool FIRST, bool DOT2, bool XMAX = false>
 SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][D + 8], short (*v_lds)[D][SAT_ATT_ROW], const bf16x8 (&qf)[D / 16][NP],
                                   f32x16 (&oacc)[D / 32], f32x16& negm, float& mb, float& l_run, int l31, int hi, int kperm, int nvalid) {
     f32x16 sacc[NKB];
@@ -343,7 +354,7 @@ SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][D + 8], short (*v_ld
                 const int key = kb * 32 + (r & 7) + 8 * hi + 16 * (r >> 3);
                 if (!MASK || key < nvalid) tmax = fmaxf(tmax, sacc[kb][r]);      // only the last tile holds padded keys (block-uniform)
             }
-        return sat_att_halfmax(tmax);
+        return XMAX ? sat_att_halfmax_x(tmax) : sat_att_halfmax(tmax);
     };
     static_assert(!DOT2 || NP == 1, "the packed row sum needs single-plane (bf16) probabilities");
     float ps0 = 0.0f, ps1 = 0.0f;
@@ -435,6 +446,105 @@ SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][D + 8], short (*v_ld
     SAT_SETPRIO(0);
 }
 
+// Sliding window (sat_attention_fwd_window; inference only): query i sees key j iff (left < 0 or j >= i - left) and (right < 0 or
+// j <= i + right) — flash-attn's window_size.  An EDGE tile of the windowed kernel — one that some row of the wave sees only in part, be
+// it by the band or by the end of the sequence — takes this body: lane-local visible key interval [vlo, vhi] (tile-relative, inclusive;
+// the band intersected with key < N, the per-lane form of sat_attn_fwd_tile's block-uniform nvalid), raw scores (C = 0), the TRUE row
+// max over the visible scores every time (a wave meets two or three such tiles, so the deferred max of the full-tile body buys nothing
+// here), and P = 0 outside the interval BEFORE the row sum and the packing: an out-of-band score may be anything, inf included, and
+// reaches neither the max nor the sums.  A row that has seen no key yet carries mb = SAT_ATT_NOMAX (finite), and every quantity of such a
+// row stays finite and zero: alpha = exp2(NOMAX - NOMAX) = 1 on l_run = 0 and O = 0 while nothing is visible, exp2(NOMAX - m) = 0 at its
+// first visible key.  negm of such a row is unusable by the full-tile body, which the kernel therefore enters only once every row of the
+// wave has seen a key (below).
+#define SAT_ATT_NOMAX (-1.0e30f)
+SAT_DEVICE int sat_att_imin(int a, int b) { return a < b ? a : b; }
+SAT_DEVICE int sat_att_imax(int a, int b) { return a > b ? a : b; }
+template <int D, int NP, int NKB, bool DOT2>
+SAT_DEVICE void sat_attn_fwd_tile_win(short (*k_lds)[SAT_ATT_T][D + 8], short (*v_lds)[D][SAT_ATT_ROW], const bf16x8 (&qf)[D / 16][NP],
+                                      f32x16 (&oacc)[D / 32], f32x16& negm, float& mb, float& l_run, int l31, int hi, int kperm, int vlo, int vhi) {
+    static_assert(!DOT2 || NP == 1, "the packed row sum needs single-plane (bf16) probabilities");
+    f32x16 sacc[NKB];
+    SAT_SETPRIO(1);
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < D / 16; ++s) {
+            bf16x8 ka[NP];
+#pragma unroll
+            for (int pl = 0; pl < NP; ++pl) ka[pl] = sat_att_frag_rm(k_lds[pl], kb * 32 + kperm, 16 * s + 8 * hi);
+            sacc[kb] = sat_att_mma<NP>(ka, qf[s], sacc[kb]);
+        }
+    }
+    SAT_SETPRIO(0);
+    float tmax = SAT_ATT_NOMAX;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = kb * 32 + (r & 7) + 8 * hi + 16 * (r >> 3);
+            if (key >= vlo && key <= vhi) tmax = fmaxf(tmax, sacc[kb][r]);
+        }
+    const float mnew = fmaxf(mb, sat_att_halfmax_x(tmax));
+    const float alpha = sat_exp2(mb - mnew);
+    mb = mnew;
+    l_run *= alpha;
+#pragma unroll
+    for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) negm[r] = -mnew;
+    float ps0 = 0.0f, ps1 = 0.0f;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = kb * 32 + (r & 7) + 8 * hi + 16 * (r >> 3);
+            const float e = sat_exp2(sacc[kb][r] - mnew);
+            sacc[kb][r] = (key >= vlo && key <= vhi) ? e : 0.0f;
+            if (!DOT2) {
+                if (r & 1) ps1 += sacc[kb][r];
+                else ps0 += sacc[kb][r];
+            }
+        }
+    bf16x8 pbs[DOT2 ? NKB : 1][2];
+    if (DOT2) {
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                bf16x8 one[NP];
+                sat_att_pack<NP>(sacc[kb], u, one);
+                pbs[DOT2 ? kb : 0][u] = one[0];
+                const u32x4 w = __builtin_bit_cast(u32x4, one[0]);
+                ps0 = sat_att_sum2(w[0], ps0);
+                ps1 = sat_att_sum2(w[1], ps1);
+                ps0 = sat_att_sum2(w[2], ps0);
+                ps1 = sat_att_sum2(w[3], ps1);
+            }
+    }
+    l_run += ps0 + ps1;
+    SAT_SETPRIO(1);
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            bf16x8 pb[NP];
+            if (DOT2) pb[0] = pbs[DOT2 ? kb : 0][u];
+            else sat_att_pack<NP>(sacc[kb], u, pb);
+#pragma unroll
+            for (int t = 0; t < D / 32; ++t) {
+                bf16x8 va[NP];
+#pragma unroll
+                for (int pl = 0; pl < NP; ++pl) va[pl] = sat_att_frag_rm(v_lds[pl], t * 32 + l31, kb * 32 + 16 * u + 8 * hi);
+                oacc[t] = sat_att_mma<NP>(va, pb, oacc[t]);
+            }
+        }
+    SAT_SETPRIO(0);
+}
+
 // The forward at head dim D = 64 / 128, NW waves of 32 queries per workgroup.  One wave owns 32 queries, 64-key tiles go through LDS, the
 // products are swapped (S^T = K Q^T, O^T += V^T P^T) so that a softmax row is lane-local, and the tile function above does the rest.  What
 // D sets: D / 16 16-wide k-steps for Q (qf[D / 16][NP]), D / 32 32-row blocks of O^T (oacc[D / 32]), a K tile of [64][D + 8] (144 B /
@@ -455,7 +565,13 @@ SAT_DEVICE void sat_attn_fwd_tile(short (*k_lds)[SAT_ATT_T][D + 8], short (*v_ld
 //                   instantiation cannot meet without spilling, and a single-buffered lone workgroup would expose every tile's
 //                   global-load latency; this is the 1e-3 parity mode, so it keeps the simple pipeline of D = 64 instead.
 // There is no backward at head dim 128: sat_attention_bwd refuses it (the two-plane dK / dV tile already needs TQ = 32 to fit LDS at D = 64).
-template <typename T, int NP, int D, int NW>
+// WIN: the sliding-window instantiations (sat_attention_fwd_window; NW = 4 only).  The workgroup stages and walks only the key tiles that
+// meet [first query - left, last query + right] within [0, N): the register-to-LDS pipeline starts at the first of them.  A wave takes
+// part in every staging store and barrier of that walk but does math only on the tiles that meet its own 32 queries' band: a tile that
+// every one of its rows sees whole, entered after every row has seen a key, runs the dense full-tile body (sat_attn_fwd_tile, deferred
+// max and all); every other one — the wave's first tile always among them, which is why there is no FIRST instantiation here: the first
+// tile is a property of the wave, not of the workgroup — runs sat_attn_fwd_tile_win.  WIN = false compiles to the dense kernel as it was.
+template <typename T, int NP, int D, int NW, bool WIN = false>
 __global__ void __launch_bounds__(64 * NW)
 #if !defined(SAT_HIPEMU)
 __attribute__((amdgpu_waves_per_eu(D == 64 ? 3 : NP == 1 ? 2 : 1)))      // the occupancy each shape's registers must leave room for (above)
@@ -556,6 +672,41 @@ sat_attn_fwd_kernel(SatAttnParams p) {
                 *reinterpret_cast<bf16x8*>(&v_lds2[buf][pl][vrow[j]][vpart[j] * 8]) = vreg[pl][j];
             }
     };
+    if constexpr (WIN) {
+        // self-attention: Nq == Nk == N.  Inclusive key ranges; the host passes each side as -1 or as a value in [0, N - 2]
+        const int wl = p.window_left, wr = p.window_right, nlast = p.Nk - 1;
+        const int gq0 = blockIdx.x * QWG, gq1 = sat_att_imin(gq0 + QWG, p.Nq) - 1;              // the workgroup's queries (gq0 < Nq: the grid)
+        const int g_lo = wl < 0 ? 0 : sat_att_imax(gq0 - wl, 0), g_hi = wr < 0 ? nlast : sat_att_imin(gq1 + wr, nlast);
+        const int kbeg = g_lo & ~(SAT_ATT_T - 1), kend = g_hi & ~(SAT_ATT_T - 1);      // first key of the first / last tile: kend + 64 <= Nkp
+        const int wq0 = gq0 + wave * 32, wq1 = sat_att_imin(wq0 + 31, p.Nq - 1);                // the wave's queries (when w_ok)
+        const int w_lo = wl < 0 ? 0 : sat_att_imax(wq0 - wl, 0), w_hi = wr < 0 ? nlast : sat_att_imin(wq1 + wr, nlast);        // keys SOME row of the wave sees
+        const int all_lo = wl < 0 ? 0 : sat_att_imax(wq1 - wl, 0), all_hi = wr < 0 ? nlast : sat_att_imin(wq0 + wr, nlast);    // keys EVERY row of the wave sees
+        const int qc = sat_att_imin(qrow, p.Nq - 1);      // a padded row (zero Q, never stored) borrows the last query's band: it always sees a key
+        const int lane_lo = wl < 0 ? 0 : qc - wl, lane_hi = wr < 0 ? nlast : sat_att_imin(qc + wr, nlast);
+        mb = SAT_ATT_NOMAX;
+        tile_load(kbeg);
+        tile_store(0);
+        if (kbeg < kend) tile_load(kbeg + SAT_ATT_T);
+        __syncthreads();
+        int buf = 0;
+        for (int k0 = kbeg; k0 <= kend; k0 += SAT_ATT_T, buf ^= 1) {
+            if (k0 < kend) {
+                tile_store(buf ^ 1);
+                if (k0 + SAT_ATT_T < kend) tile_load(k0 + 2 * SAT_ATT_T);
+            }
+            if (w_ok && k0 + SAT_ATT_T - 1 >= w_lo && k0 <= w_hi) {      // wave-uniform: the tile meets this wave's band
+                // full-tile body: every row sees all 64 keys, and the tile before this one (visited: it holds all_lo >= w_lo) gave the
+                // row with the highest lower edge, hence every row, its first key — mb and negm are true running maxima
+                if (k0 - 1 >= all_lo && k0 + SAT_ATT_T - 1 <= all_hi)
+                    sat_attn_fwd_tile<D, NP, 2, false, false, NP == 1, true>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, SAT_ATT_T);
+                else if (w_hi - k0 >= 32)
+                    sat_attn_fwd_tile_win<D, NP, 2, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, lane_lo - k0, lane_hi - k0);
+                else
+                    sat_attn_fwd_tile_win<D, NP, 1, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, lane_lo - k0, lane_hi - k0);
+            }
+            __syncthreads();
+        }
+    } else {
     tile_load(0);
     tile_store(0);
     if (SAT_ATT_T < p.Nk) tile_load(SAT_ATT_T);
@@ -591,6 +742,7 @@ sat_attn_fwd_kernel(SatAttnParams p) {
             sat_attn_fwd_tile<D, NP, 1, true, false, NP == 1>(k_lds2[buf], v_lds2[buf], qf, oacc, negm, mb, l_run, l31, hi, kperm, rem);
         }
     }
+    }      // !WIN
 
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv_l = 1.0f / l_tot;
@@ -1588,6 +1740,39 @@ extern "C" int sat_attention_fwd(const short* q_hi, const short* q_lo, const sho
         else SAT_LAUNCH((sat_attn_fwd_kernel<short, 1, 64, 4>), grid, dim3(256), stream, p);
     }
     return sat_check_launch("sat_attention_fwd");
+}
+
+// sat_attention_fwd for self-attention under a sliding window (flash-attn's window_size = (left, right): query i sees key j iff
+// (left < 0 or j >= i - left) and (right < 0 or j <= i + right); -1 = unbounded).  Inference only: there is no windowed backward, no
+// window on cross-attention (Nq != Nk leaves the alignment of the band open), and no windowed variant of the 64-query kernel, of the
+// 8-wave head dim 128 shape or of the short-key kernels — a windowed call always takes the 4-wave sat_attn_fwd_kernel<..., WIN = true>.
+// A side that is -1 or >= N - 1 hides nothing and is normalised to unbounded; with both sides unbounded this IS sat_attention_fwd.
+extern "C" int sat_attention_fwd_window(const short* q_hi, const short* q_lo, const short* k_hi, const short* k_lo,
+                                        const short* vt_hi, const short* vt_lo, void* o, float* lse, int B, int H, int Hkv,
+                                        int Nq, int Nk, int Nqp, int Nkp, int head_dim, float scale, int dtype, void* stream,
+                                        int window_left, int window_right) {
+    if (sat_attn_check(B, H, Hkv, Nq, Nk, Nqp, Nkp, head_dim, dtype, "sat_attention_fwd_window: empty shape", true)) return 1;
+    if (Nq != Nk) { sat_set_error("sat_attention_fwd_window: the sliding window is self-attention only (Nq must equal Nk; no window on cross-attention)"); return 1; }
+    if (window_left < -1 || window_right < -1) { sat_set_error("sat_attention_fwd_window: window sides must be >= -1 (-1 = unbounded)"); return 1; }
+    if (dtype == 3) { sat_set_error("sat_attention_fwd_window: dtype 3 (64 queries per wave) has no windowed kernel"); return 1; }
+    if (window_left >= Nk - 1) window_left = -1;
+    if (window_right >= Nk - 1) window_right = -1;
+    if (window_left < 0 && window_right < 0)
+        return sat_attention_fwd(q_hi, q_lo, k_hi, k_lo, vt_hi, vt_lo, o, lse, B, H, Hkv, Nq, Nk, Nqp, Nkp, head_dim, scale, dtype, stream);
+    if (head_dim == 128 && Nkp >= (1 << 23)) { sat_set_error("attention: head_dim == 128 serves fewer than 2^23 keys"); return 1; }
+    SatAttnParams p{};
+    p.q_rm[0] = q_hi; p.q_rm[1] = q_lo; p.k_rm[0] = k_hi; p.k_rm[1] = k_lo; p.v_tr[0] = vt_hi; p.v_tr[1] = vt_lo;
+    p.o = o; p.lse = lse; p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = Nq; p.Nk = Nk; p.Nqp = Nqp; p.Nkp = Nkp; p.scale = scale;
+    p.window_left = window_left; p.window_right = window_right;
+    dim3 grid(sat_cdiv(Nq, 128), H, B);
+    if (head_dim == 128) {
+        if (dtype == 0) SAT_LAUNCH((sat_attn_fwd_kernel<float, 2, 128, 4, true>), grid, dim3(256), stream, p);
+        else SAT_LAUNCH((sat_attn_fwd_kernel<short, 1, 128, 4, true>), grid, dim3(256), stream, p);
+    } else {
+        if (dtype == 0) SAT_LAUNCH((sat_attn_fwd_kernel<float, 2, 64, 4, true>), grid, dim3(256), stream, p);
+        else SAT_LAUNCH((sat_attn_fwd_kernel<short, 1, 64, 4, true>), grid, dim3(256), stream, p);
+    }
+    return sat_check_launch("sat_attention_fwd_window");
 }
 
 extern "C" int sat_attention_rowdot(const void* dout, const void* out, float* dsum, int B, int H, int Nq, int dtype,

@@ -1039,15 +1039,42 @@ class SatOps:
                                                _ptr(tr_hi), _ptr(tr_lo), b, h, n, npad, d, dt, self._stream(t)))
         return {"rm": (rm_hi, rm_lo), "tr": (tr_hi, tr_lo), "n": n, "np": npad, "dt": dt, "d": d}
 
-    def attention(self, q, k, v, scale, need_lse=False, return_planes=False):
+    @staticmethod
+    def attn_window(window, nq, nk):
+        """Validate a sliding window — flash-attn's window_size (left, right): query i sees key j iff (left < 0 or j >= i - left) and
+        (right < 0 or j <= i + right), -1 = unbounded — and normalise it: None when it hides nothing (absent, or both sides -1 or
+        >= N - 1: the call is then the dense one), else (left, right) with every unbounded side as -1."""
+        if window is None:
+            return None
+        try:
+            left, right = (int(w) for w in window)
+            ok = all(int(w) == w for w in window)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"attention: window must be a pair of integers (left, right), got {window!r}")
+        if left < -1 or right < -1:
+            raise ValueError(f"attention: window sides must be >= -1 (-1 = unbounded), got {window!r}")
+        if nq != nk:
+            raise NotImplementedError("attention: the sliding window is self-attention only (Nq == Nk); a window on cross-attention is not built")
+        left = -1 if left >= nk - 1 else left
+        right = -1 if right >= nk - 1 else right
+        return None if left < 0 and right < 0 else (left, right)
+
+    def attention(self, q, k, v, scale, need_lse=False, return_planes=False, window=None):
         """q: (B, H, Nq, D) k, v: (B, Hkv, Nk, D) — any strides with the head dim contiguous; D = 64, or 128 (inference only: the
         general forward kernel in fp32 and bf16; no planes for a backward, no short-key kernel).
+        window: sliding window (left, right) for self-attention (attn_window; inference only: there is no windowed backward) — always on
+        the 32-query general kernel (sat_attention_fwd_window), whatever cross_kernels and attn_q64 say.
         Returns o: (B, Nq, H*D) [, lse (B, H, Nq) fp32] [, planes dict for the backward]."""
         dt = self._dt(q, k, v)
         b, h, nq, d = q.shape
         _, hk, nk, _ = k.shape
         if k.shape[3] != d or v.shape[3] != d:
             raise ValueError("attention: q, k and v must share the head dim")
+        if window is not None and return_planes:
+            raise NotImplementedError("attention: the sliding window is inference-only (there is no windowed backward to keep planes for)")
+        window = self.attn_window(window, nq, nk)
         if d != 64 and return_planes:
             raise NotImplementedError(f"attention: head dim {d} is inference-only (there is no backward to keep planes for)")
         qp = self.attn_planes(q, row_major=True, transposed=return_planes)
@@ -1055,7 +1082,11 @@ class SatOps:
         vp = self.attn_planes(v, row_major=return_planes, transposed=True)
         o = torch.empty(b, nq, h * d, dtype=q.dtype, device=q.device)
         lse = torch.empty(b, h, nq, dtype=torch.float32, device=q.device) if (need_lse or return_planes) else None
-        if self.cross_ok(h, hk, nk, d, dt):      # short key sequence (the DiT's cross-attention): all keys resident, one-pass softmax
+        if window is not None:      # never the short-key kernel, never 64 queries per wave: neither has a windowed variant
+            self._chk(self.lib.sat_attention_fwd_window(_ptr(qp["rm"][0]), _ptr(qp["rm"][1]), _ptr(kp["rm"][0]), _ptr(kp["rm"][1]),
+                                                        _ptr(vp["tr"][0]), _ptr(vp["tr"][1]), _ptr(o), _ptr(lse), b, h, hk, nq, nk,
+                                                        qp["np"], kp["np"], d, float(scale), dt, self._stream(q), window[0], window[1]))
+        elif self.cross_ok(h, hk, nk, d, dt):      # short key sequence (the DiT's cross-attention): all keys resident, one-pass softmax
             self._chk(self.lib.sat_attention_cross_fwd(_ptr(qp["rm"][0]), _ptr(kp["rm"][0]), _ptr(vp["tr"][0]), _ptr(o), _ptr(lse), b, h, hk,
                                                        nq, nk, qp["np"], kp["np"], d, float(scale), self._stream(q)))
         else:
@@ -1532,15 +1563,19 @@ class SatOps:
                                              self._stream(x)))
         return out
 
-    def attention_planes(self, q_rm, k_rm, v_tr, nq, nk, scale, out_dtype=torch.bfloat16):
+    def attention_planes(self, q_rm, k_rm, v_tr, nq, nk, scale, out_dtype=torch.bfloat16, window=None):
         """Attention forward straight from bf16 operand planes (gemm_heads_bf16): q_rm (B,H,Npq,64), k_rm (B,Hkv,Npk,64),
-        v_tr (B,Hkv,64,Npk) -> o (B, Nq, H*64)."""
+        v_tr (B,Hkv,64,Npk) -> o (B, Nq, H*64).  window: as attention()."""
         b, h, npq, d = q_rm.shape
         hk, npk = k_rm.shape[1], k_rm.shape[2]
+        window = self.attn_window(window, nq, nk)
         o = torch.empty(b, nq, h * d, dtype=out_dtype, device=q_rm.device)
         if out_dtype != torch.bfloat16:
             raise TypeError("attention_planes produces bf16")
-        if self.cross_ok(h, hk, nk, d, 1):
+        if window is not None:
+            self._chk(self.lib.sat_attention_fwd_window(_ptr(q_rm), None, _ptr(k_rm), None, _ptr(v_tr), None, _ptr(o), None, b, h, hk, nq, nk,
+                                                        npq, npk, d, float(scale), 1, self._stream(q_rm), window[0], window[1]))
+        elif self.cross_ok(h, hk, nk, d, 1):
             self._chk(self.lib.sat_attention_cross_fwd(_ptr(q_rm), _ptr(k_rm), _ptr(v_tr), _ptr(o), None, b, h, hk, nq, nk, npq, npk, d,
                                                        float(scale), self._stream(q_rm)))
         else:

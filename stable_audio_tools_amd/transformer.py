@@ -11,10 +11,12 @@ linear.Linear on the native MFMA GEMM (csrc/gemm.hip) with the head split / rota
 residual work of the block fused into the GEMM epilogues — no library GEMM.  Attention(qk_norm="ln" | "l2")
 (attn_kwargs: {"qk_norm": ...}; the per-head q / k normalisation before the rotary, transformer.py:374-376,
 :485-489) runs inside the same projection epilogue in bf16 inference (sat_gemm_qkv_norm_bf16) and on the
-sat_qk_norm_fwd / sat_qk_norm_bwd kernels in training and fp32.  Options of the reference that the Stable
-Audio DiT configs never enable (qk_norm="dyt", differential attention, conformer, layer_scale, memory
-tokens, sliding window, causal, flex-attention masks, abs/sinusoidal position embeddings) raise
-NotImplementedError.
+sat_qk_norm_fwd / sat_qk_norm_bwd kernels in training and fp32.  ContinuousTransformer(sliding_window=[left, right])
+(flash-attn's window_size on every layer's self-attention, transformer.py:436, :845) runs on the windowed forward
+kernel (sat_attention_fwd_window) in inference, fp32 and bf16, head dims 64 and 128; training with a window, a
+window on cross-attention and a window over an fp8 input projection raise NotImplementedError.  So do the options
+of the reference that the Stable Audio DiT configs never enable (qk_norm="dyt", differential attention, conformer,
+layer_scale, memory tokens, causal, flex-attention masks, abs/sinusoidal position embeddings).
 
 Forward AND backward run on the HIP kernels: every fused operator is a torch.autograd.Function whose
 backward calls the matching kernel (LayerNorm+adaLN, rotary transpose, attention dQ / dK,dV with
@@ -466,6 +468,20 @@ class FeedForward(nn.Module):
         return self.ff[2](self.ff[0](x), res=res)
 
 
+def _sliding_window(window):
+    """None, or a sliding window as the tuple (left, right) of integers >= -1 (flash-attn's window_size; -1 = unbounded): query i sees
+    key j iff (left < 0 or j >= i - left) and (right < 0 or j <= i + right).  Anything else is a ValueError."""
+    if window is None:
+        return None
+    try:
+        ok = len(window) == 2 and all(not isinstance(w, bool) and int(w) == w for w in window)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or min(int(w) for w in window) < -1:
+        raise ValueError(f"sliding_window must be a pair of integers [left, right], each >= -1 (-1 = unbounded), got {window!r}")
+    return int(window[0]), int(window[1])
+
+
 class Attention(nn.Module):
     def __init__(self, dim, dim_heads=64, dim_context=None, causal=False, zero_init_output=True, qk_norm="none",
                  differential=False, feat_scale=False):
@@ -530,11 +546,13 @@ class Attention(nn.Module):
             return ops.gemm_heads_fp8(qx, qw, alpha, cs, heads, nb, ntok, sec0, nsec, reuse=tag, col_alpha=calpha)
         return ops.gemm_heads_bf16(x2, lin.lowp_weight(), cs, heads, nb, ntok, sec0, nsec, reuse=tag)
 
-    def _forward_hd128(self, x, kv_input, rotary_pos_emb, res, norm):
+    def _forward_hd128(self, x, kv_input, rotary_pos_emb, res, norm, window=None):
         """Head dim 128 (inference only; fp32 and bf16): projection through the Linear, then the standalone norm + rotary kernel
         (sat_qk_norm_fwd_hd) or the in-place rotary, then plane preparation and the forward kernel of csrc/attention.hip at D = 128
         (ops.attention), then to_out with the residual epilogue.  The projection-epilogue fusion of the head dim 64 bf16 path
-        (gemm_heads_bf16) is not built at 128."""
+        (gemm_heads_bf16) is not built at 128.
+        Nothing below depends on the head dim: the fp32 no-grad self-attention under a sliding window (`window`, checked by forward)
+        takes this path at head dim 64 too."""
         if torch.is_grad_enabled():
             raise NotImplementedError("head dim 128 is inference-only (there are no backward kernels at this head dim): run the model under torch.no_grad()")
         cross = hasattr(self, "to_q")
@@ -572,10 +590,12 @@ class Attention(nn.Module):
             q = qk[..., :hd].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
             k = qk[..., hd:].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
             v = qkv[..., 2 * hd:].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
-        return self.to_out(ops.attention(q, k, v, self.scale), res=res)
+        return self.to_out(ops.attention(q, k, v, self.scale, window=window), res=res)
 
-    def forward(self, x, context=None, rotary_pos_emb=None, causal=None, res=None, **unsupported):
-        """res: the residual stream, added in the output projection's epilogue (x = x + attn(...), transformer.py:703-707)."""
+    def forward(self, x, context=None, rotary_pos_emb=None, causal=None, res=None, flash_attn_sliding_window=None, **unsupported):
+        """res: the residual stream, added in the output projection's epilogue (x = x + attn(...), transformer.py:703-707).
+        flash_attn_sliding_window: (left, right), flash-attn's window_size (transformer.py:436) — self-attention under torch.no_grad()
+        only; applied always (the reference drops it with a warning where the flash-attn package is missing, transformer.py:414-415)."""
         for k, v in unsupported.items():
             if v is not None:
                 raise NotImplementedError(f"Attention.forward({k}=...) is not on the HIP path")
@@ -589,8 +609,20 @@ class Attention(nn.Module):
         norm = self._norm()
         if norm is not None and (isinstance(x, _linear.Fp8Rows) or first.fp8 or (cross and self.to_kv.fp8)):
             raise NotImplementedError("qk_norm on an fp8 input projection: the fp8 heads GEMM has no norm epilogue (keep to_qkv / to_q / to_kv in bf16)")
+        window = _sliding_window(flash_attn_sliding_window)
+        if window is not None:
+            if cross:
+                raise NotImplementedError("a sliding window on cross-attention is not built (the window is self-attention only: Nq == Nk)")
+            if torch.is_grad_enabled():
+                raise NotImplementedError("the sliding window is inference-only (there is no windowed backward kernel; training with a "
+                                          "window is not built): run the model under torch.no_grad()")
+            if isinstance(x, _linear.Fp8Rows) or first.fp8:
+                raise NotImplementedError("a sliding window on an fp8 input projection is not built (keep to_qkv in bf16)")
+            window = _ops().attn_window(window, n, n)      # None when it hides nothing at this length: the dense paths, bit for bit
         if dh == 128:
-            return self._forward_hd128(x, kv_input, rotary_pos_emb, res, norm)
+            return self._forward_hd128(x, kv_input, rotary_pos_emb, res, norm, window)
+        if window is not None and not (_lowp(x, first.weight) and first.lowp_weight() is not None):
+            return self._forward_hd128(x, kv_input, rotary_pos_emb, res, norm, window)      # fp32: the standalone kernels, at head dim 64
         if not torch.is_grad_enabled() and _lowp(x, first.weight) and first.lowp_weight() is not None \
                 and (not cross or self.to_kv.lowp_weight() is not None):
             # inference, bf16: head split, rotary and the attention kernel's operand planes come straight out of the
@@ -629,7 +661,7 @@ class Attention(nn.Module):
             else:
                 cs = rotary_pos_emb[0] if rotary_pos_emb is not None else None
                 pl = self._heads(ops, self.to_qkv, x2, cs, h, b, n, 0, 3, "self", norm)
-                out = ops.attention_planes(pl["q"], pl["k"], pl["v_tr"], n, n, self.scale)
+                out = ops.attention_planes(pl["q"], pl["k"], pl["v_tr"], n, n, self.scale, window=window)
             return self.to_out(out, res=res)
         if _ops().train_fused_nodes and dh == 64:
             if cross:
@@ -692,18 +724,22 @@ class TransformerBlock(nn.Module):
         if global_cond_dim is not None:
             self.to_scale_shift_gate = nn.Parameter(torch.randn(6 * dim) / dim ** 0.5)
 
-    def forward(self, x, context=None, global_cond=None, rotary_pos_emb=None, **unsupported):
+    def forward(self, x, context=None, global_cond=None, rotary_pos_emb=None, self_attention_flash_sliding_window=None, **unsupported):
+        """self_attention_flash_sliding_window: (left, right) for self_attn alone (transformer.py:683, :704; inference only);
+        cross_attention_flash_sliding_window, like every other option of the reference's block forward, raises."""
         for k, v in unsupported.items():
             if v is not None:
                 raise NotImplementedError(f"TransformerBlock.forward({k}=...) is not on the HIP path")
         d = self.dim
+        sw = self_attention_flash_sliding_window
         if self.global_cond_dim is not None and self.global_cond_dim > 0 and global_cond is not None:
             # adaLN: (to_scale_shift_gate + global_cond).chunk(6)   (transformer.py:677)
             # cast to the activation dtype: under bf16 autocast the fp32 parameter promotes the sum to fp32 while x is bf16
             mod = (self.to_scale_shift_gate + global_cond).to(x.dtype).contiguous()   # (B, 6D)
             scale_self, shift_self, gate_self = mod[:, 0:d], mod[:, d:2 * d], mod[:, 2 * d:3 * d]
             scale_ff, shift_ff, gate_ff = mod[:, 3 * d:4 * d], mod[:, 4 * d:5 * d], mod[:, 5 * d:6 * d]
-            h = self.self_attn(self.pre_norm(x, scale_self, shift_self, fp8_for=_fp8_rows_for(self.self_attn, self.self_attn.to_qkv)), rotary_pos_emb=rotary_pos_emb)
+            h = self.self_attn(self.pre_norm(x, scale_self, shift_self, fp8_for=_fp8_rows_for(self.self_attn, self.self_attn.to_qkv)), rotary_pos_emb=rotary_pos_emb,
+                               flash_attn_sliding_window=sw)
             x = _GateResidualFn.apply(h, gate_self, x)                           # h*sigmoid(1-gate)+x  (:684-686)
             if context is not None and self.cross_attend:
                 x = self.cross_attn(self.cross_attend_norm(x, fp8_for=_fp8_rows_for(self.cross_attn, self.cross_attn.to_q)), context=context, res=x)   # never modulated (:688-689)
@@ -714,13 +750,14 @@ class TransformerBlock(nn.Module):
             if torch.is_grad_enabled() and x.requires_grad and _ops().train_fused_nodes and _ops().ln_residual:
                 # training: each norm also hands x through, so the residual path's gradient is added inside the LayerNorm backward kernel
                 h, xr = self.pre_norm.with_residual(x)
-                x = self.self_attn(h, rotary_pos_emb=rotary_pos_emb, res=xr)
+                x = self.self_attn(h, rotary_pos_emb=rotary_pos_emb, res=xr, flash_attn_sliding_window=sw)
                 if context is not None and self.cross_attend:
                     h, xr = self.cross_attend_norm.with_residual(x)
                     x = self.cross_attn(h, context=context, res=xr)
                 h, xr = self.ff_norm.with_residual(x)
                 return self.ff(h, res=xr)
-            x = self.self_attn(self.pre_norm(x, fp8_for=_fp8_rows_for(self.self_attn, self.self_attn.to_qkv)), rotary_pos_emb=rotary_pos_emb, res=x)   # residual adds live in
+            x = self.self_attn(self.pre_norm(x, fp8_for=_fp8_rows_for(self.self_attn, self.self_attn.to_qkv)), rotary_pos_emb=rotary_pos_emb, res=x,   # residual adds live in
+                               flash_attn_sliding_window=sw)
             if context is not None and self.cross_attend:                                                                 # the output projections' epilogues
                 x = self.cross_attn(self.cross_attend_norm(x, fp8_for=_fp8_rows_for(self.cross_attn, self.cross_attn.to_q)), context=context, res=x)
             x = self.ff(self.ff_norm(x, fp8_for=self.ff.ff[0].proj), res=x)
@@ -733,8 +770,8 @@ class ContinuousTransformer(nn.Module):
                  zero_init_branch_outputs=True, conformer=False, use_sinusoidal_emb=False, use_abs_pos_emb=False,
                  abs_pos_emb_max_length=10000, num_memory_tokens=0, sliding_window=None, **kwargs):
         super().__init__()
-        if causal or conformer or use_sinusoidal_emb or use_abs_pos_emb or num_memory_tokens or sliding_window is not None:
-            raise NotImplementedError("causal / conformer / abs-pos-emb / memory tokens / sliding window are not on the HIP path")
+        if causal or conformer or use_sinusoidal_emb or use_abs_pos_emb or num_memory_tokens:
+            raise NotImplementedError("causal / conformer / abs-pos-emb / memory tokens are not on the HIP path")
         self.dim, self.depth, self.causal = dim, depth, False
         self.layers = nn.ModuleList([])
         self.project_in = Linear(dim_in, dim, bias=False) if dim_in is not None else nn.Identity()
@@ -745,7 +782,11 @@ class ContinuousTransformer(nn.Module):
         if global_cond_dim is not None:
             self.global_cond_embedder = nn.Sequential(Linear(global_cond_dim, dim), nn.SiLU(), Linear(dim, dim * 6))
         self.final_cross_attn_ix = final_cross_attn_ix
-        self.sliding_window = None
+        # [left, right] for every layer's self-attention (transformer.py:777, :845): validated here, kept as given (None, or the list /
+        # tuple of the config); inference only — a forward in grad mode raises in Attention.forward.  Prepended tokens are ordinary
+        # sequence positions, as in the reference.
+        _sliding_window(sliding_window)
+        self.sliding_window = sliding_window
         self.checkpointing = False      # opt-in activation recompute per layer (see forward)
         for i in range(depth):
             should_cross_attend = cross_attend and (final_cross_attn_ix == -1 or i <= final_cross_attn_ix)
@@ -772,9 +813,10 @@ class ContinuousTransformer(nn.Module):
         ckpt = self.checkpointing and use_checkpointing and torch.is_grad_enabled()
         for layer_ix, layer in enumerate(self.layers):
             if ckpt:
-                x = torch.utils.checkpoint.checkpoint(layer, x, rotary_pos_emb=rotary, global_cond=global_cond, use_reentrant=False, **kwargs)
+                x = torch.utils.checkpoint.checkpoint(layer, x, rotary_pos_emb=rotary, global_cond=global_cond, use_reentrant=False,
+                                                      self_attention_flash_sliding_window=self.sliding_window, **kwargs)
             else:
-                x = layer(x, rotary_pos_emb=rotary, global_cond=global_cond, **kwargs)
+                x = layer(x, rotary_pos_emb=rotary, global_cond=global_cond, self_attention_flash_sliding_window=self.sliding_window, **kwargs)
             if return_info:
                 info["hidden_states"].append(x)
             if exit_layer_ix is not None and layer_ix == exit_layer_ix:

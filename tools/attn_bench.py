@@ -4,7 +4,10 @@ kernel shapes of sat_attention_fwd (32 / 64 queries per wave, round 6), and what
     python tools/attn_bench.py --head-dim 128      the head dim 128 forward (bf16 at N = 1025 / 6145, fp32 at N = 1025), each next to the
                                                    head dim 64 32-query kernel at EQUAL FLOPs (twice the heads, same N) in the same
                                                    process; median of 5 timings (HIP events around graph replays), plus the plane
-                                                   preparation of q / k / v at 128"""
+                                                   preparation of q / k / v at 128
+    python tools/attn_bench.py --window 63 64      the sliding-window launch (sat_attention_fwd_window) beside the dense ones at the same
+                                                   shape: bf16, N = 1025 and 6145, head dims 64 and 128, one process, six alternated
+                                                   rounds of (windowed, dense basic, dense auto); median of 5 timings each"""
 import argparse
 import json
 import sys
@@ -16,6 +19,7 @@ from stable_audio_tools_amd.ops import _ptr, get_ops
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--head-dim", type=int, default=64, choices=(64, 128))
+ap.add_argument("--window", type=int, nargs=2, metavar=("L", "R"), default=None)
 args = ap.parse_args()
 
 o = get_ops()
@@ -68,8 +72,9 @@ def head_dim_64():
     o.attn_q64 = None
 
 
-def kernel_only(b, h, n, d, dtype, auto=False):
-    """(callable launching sat_attention_fwd alone on prepared planes, callable preparing the three operands, max rel error)"""
+def kernel_only(b, h, n, d, dtype, auto=False, window=None):
+    """(callable launching sat_attention_fwd — with `window`, sat_attention_fwd_window — alone on prepared planes, callable preparing the
+    three operands, max rel error against torch's attention under the same band)"""
     q, k, v = (torch.randn(b, n, h, d, device='cuda').to(dtype).permute(0, 2, 1, 3) for _ in range(3))      # the model's (B, N, H, D) storage
     scale = d ** -0.5
     qp, kp, vp = o.attn_planes(q), o.attn_planes(k), o.attn_planes(v, row_major=False, transposed=True)
@@ -79,14 +84,19 @@ def kernel_only(b, h, n, d, dtype, auto=False):
     dt = 0 if dtype == torch.float32 else (1 if auto else 2)
 
     def launch():
-        rc = o.lib.sat_attention_fwd(_ptr(qp["rm"][0]), _ptr(qp["rm"][1]), _ptr(kp["rm"][0]), _ptr(kp["rm"][1]), _ptr(vp["tr"][0]), _ptr(vp["tr"][1]),
-                                     _ptr(out), None, b, h, h, n, n, qp["np"], kp["np"], d, scale, dt, torch.cuda.current_stream().cuda_stream)
+        common = (_ptr(qp["rm"][0]), _ptr(qp["rm"][1]), _ptr(kp["rm"][0]), _ptr(kp["rm"][1]), _ptr(vp["tr"][0]), _ptr(vp["tr"][1]),
+                  _ptr(out), None, b, h, h, n, n, qp["np"], kp["np"], d, scale, dt, torch.cuda.current_stream().cuda_stream)
+        rc = o.lib.sat_attention_fwd(*common) if window is None else o.lib.sat_attention_fwd_window(*common, *window)
         assert rc == 0, o.lib.sat_last_error()
 
     def prepare():
         o.attn_planes(q), o.attn_planes(k), o.attn_planes(v, row_major=False, transposed=True)
     launch()
-    ref = torch.nn.functional.scaled_dot_product_attention(q[:1].float(), k[:1].float(), v[:1].float(), scale=scale).permute(0, 2, 1, 3).reshape(1, n, h * d)
+    mask = None
+    if window is not None:
+        i, j = torch.arange(n, device='cuda')[:, None], torch.arange(n, device='cuda')[None, :]
+        mask = ((j >= i - window[0]) if window[0] >= 0 else (j >= 0)) & ((j <= i + window[1]) if window[1] >= 0 else (j >= 0))
+    ref = torch.nn.functional.scaled_dot_product_attention(q[:1].float(), k[:1].float(), v[:1].float(), attn_mask=mask, scale=scale).permute(0, 2, 1, 3).reshape(1, n, h * d)
     err = float((out[:1].float() - ref).abs().max() / ref.abs().max())
     return launch, prepare, err
 
@@ -116,7 +126,27 @@ def head_dim_128():
         print(json.dumps({"N": n, "dtype": rows[0]["dtype"], "hd128_over_hd64_time_at_equal_flops": round(t128 / t64, 4)}), flush=True)
 
 
-if args.head_dim == 64:
+def windowed(window):
+    for d, heads in ((64, 48), (128, 24)):
+        for n in (1025, 6145):
+            reps = 100 if n < 4000 else 40
+            kinds = {"windowed": kernel_only(2, heads // 2, n, d, torch.bfloat16, False, tuple(window)),
+                     "dense_basic": kernel_only(2, heads // 2, n, d, torch.bfloat16, False),
+                     "dense_auto": kernel_only(2, heads // 2, n, d, torch.bfloat16, True)}
+            runs = {name: [] for name in kinds}
+            for _ in range(6):      # alternate the launches: same process, same box
+                for name, (launch, _, _) in kinds.items():
+                    runs[name].append(round(median_us(launch, reps)[0], 2))
+            for name in kinds:
+                print(json.dumps({"head_dim": d, "N": n, "B*H": heads, "dtype": "bfloat16", "launch": name, "window": list(window) if name == "windowed" else None,
+                                  "us_runs": runs[name], "us_min": min(runs[name]), "us_max": max(runs[name]), "err": round(kinds[name][2], 6)}), flush=True)
+            dense = min(min(runs["dense_basic"]), min(runs["dense_auto"]))
+            print(json.dumps({"head_dim": d, "N": n, "windowed_over_dense_time": round(max(runs["windowed"]) / dense, 4)}), flush=True)
+
+
+if args.window is not None:
+    windowed(args.window)
+elif args.head_dim == 64:
     head_dim_64()
 else:
     head_dim_128()
