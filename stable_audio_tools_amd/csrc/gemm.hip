@@ -1176,11 +1176,14 @@ static int sat_gemm_dispatch_fp8(SatGemmParams& p, int epi, int f32out, int tile
     return sat_gemm_launch<128, 128, 2, 2, 2, 0, true>(p, epi, f32out, 1, stream);
 }
 
-// C = epilogue(A · B^T).  A (M, K), B (N, K) bf16 with row strides lda / ldb (elements, multiples of 8; K % 8 == 0).
+// C = epilogue(A · B^T).  A (M, K), B (N, K) bf16 with row strides lda / ldb (elements, multiples of 8; K % 8 == 0, N % 8 == 0);
+// ldc a multiple of 4 (ldc % 4 is rejected with the message that names K, N, lda, ldb); ldr / ldg / ldp multiples of 4 too (not checked):
+// the epilogue's loads and stores are 8- and 16-byte accesses.
 // epilogue: 0 store [+bias]; 1 + res; 2 * sigmoid(1 - gate[m / rows_per_gate]) + res; 3 SwiGLU over B = [value rows | gate rows]
 // (N = 2F, C is (M, F), optional pre-activation copy `pre` (M, 2F)).  out_f32: C / res / gate / pre are fp32 instead of bf16.
 // splits > 1 (epilogue 0, fp32 out, no bias): K is cut into `splits` ranges, slab z is written at C + z * M * ldc — reduce with
-// sat_reduce_splits.  zeros: >= 16 bytes of device zeros.  tile: 0 = 128 x 128 (4 waves), 1 = 256 x 128 (8 waves).
+// sat_reduce_splits.  zeros: >= 16 bytes of device zeros.  tile: 0 = 128 x 128 (4 waves), 4 = 256 x 256, 7 = 160 x 256, 8 = 128 x 128
+// (8 waves each): sat_gemm_dispatch.
 extern "C" int sat_gemm_bf16(const void* A, long long lda, const void* B, long long ldb, void* C, long long ldc, const float* bias,
                              const void* res, long long ldr, const void* gate, long long ldg, int rows_per_gate, void* pre,
                              long long ldp, const void* zeros, int M, int N, int K, int epilogue, int out_f32, int splits, int tile,
