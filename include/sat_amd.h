@@ -612,6 +612,13 @@ int sat_split_bf16x3(const float* src, long long lds, void* dst, long long ldd, 
  * objective 1 ("rectified_flow" / "rf_denoiser"): alpha = 1 - t, sigma = t, targets = noise - xs.  B <= 65535. */
 int sat_diffusion_noise(const float* x, const float* noise, const float* t, float* noised, float* targets, int B, int C, int T,
                         int objective, float inv_scale, void* stream);
+/* sat_diffusion_noise plus the inpainting conditioning of training/diffusion.py:429-438 (models/inpainting.py:11-97) in the same launch
+ * and the same read of x and noise; noised / targets are bit-equal to sat_diffusion_noise's.  segments: (B, S, 2) int32 on the device,
+ * half-open intervals [start, end) of time steps to inpaint (start >= end: unused row; intervals may overlap or leave [0, T)),
+ * 1 <= S <= 256.  concat: (B, 1 + C, T) fp32 = [mask | masked] when mask_first, else [masked | mask]; mask = 0.0 inside any interval of
+ * the item, else 1.0; masked = x * inv_scale where the mask is 1 and +0.0 where it is 0 (a select: inf / nan there do not pass). */
+int sat_diffusion_noise_inpaint(const float* x, const float* noise, const float* t, const int* segments, float* noised, float* targets,
+                                float* concat, int B, int C, int T, int S, int objective, float inv_scale, int mask_first, void* stream);
 /* res[0] = sum over selected (b, c, t) of (out - targets)^2 / count, res[1] = count = C * sum(mask) (B*C*T when mask == NULL; counted
  * in integers, stored as a float).  out: (B, C, T) fp32 (dtype 0) | bf16 (dtype 1); targets fp32; mask: (B, T) bytes, non-zero = selected.
  * Masked elements are skipped, not multiplied by zero; an empty selection gives NaN.  work: 2 * sat_masked_mse_nblocks(B, C, T) 4-byte

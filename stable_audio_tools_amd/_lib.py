@@ -151,6 +151,7 @@ SIGNATURES = {
     "sat_gate_residual_bwd": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _P]),
     # diffusion_step.hip
     "sat_diffusion_noise": (_I, [_P] * 5 + [_I] * 4 + [_F, _P]),
+    "sat_diffusion_noise_inpaint": (_I, [_P] * 7 + [_I] * 5 + [_F, _I, _P]),
     "sat_masked_mse_nblocks": (_I, [_I, _I, _I]),
     "sat_masked_mse_fwd": (_I, [_P] * 5 + [_I] * 4 + [_P]),
     "sat_masked_mse_bwd": (_I, [_P] * 6 + [_I] * 4 + [_P]),

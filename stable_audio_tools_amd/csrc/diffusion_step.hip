@@ -2,6 +2,8 @@
 // DiffusionCondTrainingWrapper.training_step, training/diffusion.py:332-487):
 //   sat_diffusion_noise   alphas / sigmas of the drawn timesteps, noised = x*alpha + noise*sigma and the v / rectified-flow targets
 //                         (:377-379, :406-420) in one pass over x and noise
+//   sat_diffusion_noise_inpaint  the same, plus the inpainting conditioning of :429-438 (models/inpainting.py:11-97) from a device
+//                         table of masked intervals: the mask channel and the masked, scaled latent, in the same pass
 //   sat_masked_mse_fwd    MSELoss with mask_key="padding_mask" (training/losses/losses.py:76-89): the mean of (out - targets)^2 over the
 //                         SELECTED elements, without the host sync of the reference's boolean indexing
 //   sat_masked_mse_bwd    its gradient, zero at masked positions
@@ -41,12 +43,11 @@ SAT_DEVICE void sat_noise_one(float xv, float nz, float alpha, float sigma, floa
     *target = objective == 0 ? nz * alpha - xs * sigma : nz - xs;
 }
 
-__global__ void __launch_bounds__(256) sat_diffusion_noise_kernel(SatNoiseParams p) {
-    __shared__ float ab[2];
-    const int b = blockIdx.y;
+// alpha / sigma of batch row b into ab[0], ab[1] (thread 0); the caller's __syncthreads() publishes them
+SAT_DEVICE void sat_noise_alpha_sigma(const float* t, int b, int objective, float* ab) {
     if (threadIdx.x == 0) {
-        const float tb = p.t[b];
-        if (p.objective == 0) {
+        const float tb = t[b];
+        if (objective == 0) {
             const float ang = tb * 1.57079632679489662f;       // t * pi / 2
             ab[0] = cosf(ang);
             ab[1] = sinf(ang);
@@ -55,6 +56,12 @@ __global__ void __launch_bounds__(256) sat_diffusion_noise_kernel(SatNoiseParams
             ab[1] = tb;
         }
     }
+}
+
+__global__ void __launch_bounds__(256) sat_diffusion_noise_kernel(SatNoiseParams p) {
+    __shared__ float ab[2];
+    const int b = blockIdx.y;
+    sat_noise_alpha_sigma(p.t, b, p.objective, ab);
     __syncthreads();
     const float alpha = ab[0], sigma = ab[1];
     const long long off = (long long)b * p.per;
@@ -107,6 +114,125 @@ extern "C" int sat_diffusion_noise(const float* x, const float* noise, const flo
     if (nx > 1024) nx = 1024;
     SAT_LAUNCH(sat_diffusion_noise_kernel, dim3((unsigned)nx, (unsigned)B), dim3(256), stream, p);
     return sat_check_launch("sat_diffusion_noise");
+}
+
+// ------------------------------------------------------------------------------------------------
+// noising + targets + inpainting conditioning.  Same grid, same arithmetic for noised / targets (sat_noise_one, sat_noise_alpha_sigma:
+// bit-equal to sat_diffusion_noise).  Item b's S intervals [start, end) are loaded into LDS once per workgroup; every lane reads the same
+// interval at the same time (an LDS broadcast).  An element's time index is its position modulo T inside its row of C*T.  The masked
+// latent is a SELECT between x * inv_scale and +0: an inf / nan inside an inpainted interval does not reach the conditioning.  A batch
+// row of `concat` is (1 + C) * T floats, so its masked-latent block may sit at another offset inside a 16-byte line than the row of x:
+// it is then written with scalar stores from the same registers.  The intervals are only compared with, never indexed by.
+// ------------------------------------------------------------------------------------------------
+#define SAT_INPAINT_MAX_SEGS 256
+
+struct SatInpaintParams {
+    SatNoiseParams n;
+    const int* segments;  // (B, S, 2)
+    float* mask;          // mask channel of batch row 0: (B, T) with row stride crow
+    float* masked;        // masked latent of batch row 0: (B, C * T) with row stride crow
+    long long crow;       // (1 + C) * T
+    int T, S;
+};
+
+SAT_DEVICE bool sat_inpaint_keep(const int* seg, int S, int tt) {
+    bool hit = false;
+    for (int s = 0; s < S; ++s) hit |= tt >= seg[2 * s] && tt < seg[2 * s + 1];
+    return !hit;
+}
+
+__global__ void __launch_bounds__(256) sat_diffusion_noise_inpaint_kernel(SatInpaintParams q) {
+    __shared__ float ab[2];
+    __shared__ int seg[2 * SAT_INPAINT_MAX_SEGS];
+    const SatNoiseParams& p = q.n;
+    const int b = blockIdx.y;
+    sat_noise_alpha_sigma(p.t, b, p.objective, ab);
+    for (int k = threadIdx.x; k < 2 * q.S; k += 256) seg[k] = q.segments[(long long)b * 2 * q.S + k];
+    __syncthreads();
+    const float alpha = ab[0], sigma = ab[1];
+    const long long off = (long long)b * p.per;
+    const float* x = p.x + off;
+    const float* nz = p.noise + off;
+    float* noised = p.noised + off;
+    float* targets = p.targets + off;
+    float* masked = q.masked + (long long)b * q.crow;
+    float* mk = q.mask + (long long)b * q.crow;
+    const long long stride = (long long)gridDim.x * 256;
+    const long long first = (long long)blockIdx.x * 256 + threadIdx.x;
+    // the mask channel: T of the row's (1 + C) * T floats
+    for (long long j = first; j < q.T; j += stride) mk[j] = sat_inpaint_keep(seg, q.S, (int)j) ? 1.0f : 0.0f;
+    // head / vector body / tail as in sat_diffusion_noise_kernel, decided by the four (B, C, T) tensors
+    const unsigned mis = (unsigned)((uintptr_t)x & 15);
+    const bool same = (mis & 3) == 0 && ((uintptr_t)nz & 15) == mis && ((uintptr_t)noised & 15) == mis && ((uintptr_t)targets & 15) == mis;
+    const bool mvec = ((uintptr_t)masked & 15) == mis;
+    long long head = same ? (long long)(((16u - mis) & 15u) >> 2) : p.per;
+    if (head > p.per) head = p.per;
+    const long long nvec = (p.per - head) >> 2;
+    const long long tail0 = head + 4 * nvec;
+    for (long long v = first; v < nvec; v += stride) {
+        const long long i = head + 4 * v;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i);
+        const f32x4 nv = *reinterpret_cast<const f32x4*>(nz + i);
+        int tt[4];
+        tt[0] = (int)(i % q.T);
+#pragma unroll
+        for (int e = 1; e < 4; ++e) tt[e] = tt[e - 1] + 1 == q.T ? 0 : tt[e - 1] + 1;
+        bool hit[4] = {false, false, false, false};
+        for (int s = 0; s < q.S; ++s) {
+            const int lo = seg[2 * s], hi = seg[2 * s + 1];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hit[e] |= tt[e] >= lo && tt[e] < hi;
+        }
+        f32x4 o, g, m;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float a, c;
+            sat_noise_one(xv[e], nv[e], alpha, sigma, p.inv_scale, p.objective, &a, &c);
+            o[e] = a;
+            g[e] = c;
+            m[e] = hit[e] ? 0.0f : xv[e] * p.inv_scale;
+        }
+        *reinterpret_cast<f32x4*>(noised + i) = o;
+        *reinterpret_cast<f32x4*>(targets + i) = g;
+        if (mvec) {
+            *reinterpret_cast<f32x4*>(masked + i) = m;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) masked[i + e] = m[e];
+        }
+    }
+    const long long nscalar = head + (p.per - tail0);
+    for (long long k = first; k < nscalar; k += stride) {
+        const long long i = k < head ? k : tail0 + (k - head);
+        float a, c;
+        sat_noise_one(x[i], nz[i], alpha, sigma, p.inv_scale, p.objective, &a, &c);
+        noised[i] = a;
+        targets[i] = c;
+        masked[i] = sat_inpaint_keep(seg, q.S, (int)(i % q.T)) ? x[i] * p.inv_scale : 0.0f;
+    }
+}
+
+extern "C" int sat_diffusion_noise_inpaint(const float* x, const float* noise, const float* t, const int* segments, float* noised,
+                                           float* targets, float* concat, int B, int C, int T, int S, int objective, float inv_scale,
+                                           int mask_first, void* stream) {
+    if (B <= 0 || C <= 0 || T <= 0) { sat_set_error("sat_diffusion_noise_inpaint: empty shape"); return 1; }
+    if (B > 65535) { sat_set_error("sat_diffusion_noise_inpaint: B > 65535"); return 1; }
+    if (S <= 0) { sat_set_error("sat_diffusion_noise_inpaint: S <= 0"); return 1; }
+    if (S > SAT_INPAINT_MAX_SEGS) { sat_set_error("sat_diffusion_noise_inpaint: S > 256"); return 1; }
+    if (objective != 0 && objective != 1) { sat_set_error("sat_diffusion_noise_inpaint: objective must be 0 (v) or 1 (rectified flow)"); return 1; }
+    if (!x || !noise || !t || !segments || !noised || !targets || !concat) { sat_set_error("sat_diffusion_noise_inpaint: null tensor"); return 1; }
+    SatInpaintParams q{};
+    q.n = SatNoiseParams{x, noise, t, noised, targets, (long long)C * T, inv_scale, objective};
+    q.segments = segments;
+    q.mask = mask_first ? concat : concat + q.n.per;
+    q.masked = mask_first ? concat + T : concat;
+    q.crow = q.n.per + T;
+    q.T = T;
+    q.S = S;
+    long long nx = sat_cdivll(q.n.per, 4096);
+    if (nx > 1024) nx = 1024;
+    SAT_LAUNCH(sat_diffusion_noise_inpaint_kernel, dim3((unsigned)nx, (unsigned)B), dim3(256), stream, q);
+    return sat_check_launch("sat_diffusion_noise_inpaint");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1741,6 +1741,27 @@ class SatOps:
                                                1.0 / float(latent_scale), self._stream(x)))
         return noised, targets
 
+    def diffusion_noise_inpaint(self, x, noise, t, segments, objective, latent_scale=1.0, mask_first=True):
+        """diffusion_noise plus the inpainting conditioning (training/diffusion.py:429-438) in the same launch: (noised, targets, concat).
+        segments: (B, S, 2) int32 on x's device, half-open intervals [start, end) of time steps to inpaint (training.random_inpaint_segments;
+        start == end: unused).  concat (B, 1 + C, T) fp32 = [mask | masked] when mask_first, else [masked | mask] — the order of the model
+        config's input_concat_ids; mask is 0.0 inside the intervals and 1.0 elsewhere, masked = x / latent_scale where the mask is 1, else 0."""
+        if objective not in self.OBJECTIVES:
+            raise ValueError(f"diffusion_noise_inpaint: unknown objective {objective!r}")
+        self._f32(x, noise, t)
+        if x.dim() != 3 or noise.shape != x.shape or tuple(t.shape) != (x.shape[0],):
+            raise ValueError("diffusion_noise_inpaint: x, noise (B, C, T) and t (B,)")
+        b, c, tt = x.shape
+        if segments.dtype != torch.int32 or segments.dim() != 3 or segments.shape[0] != b or segments.shape[2] != 2 \
+                or not segments.is_contiguous() or segments.device != x.device:
+            raise ValueError("diffusion_noise_inpaint: segments must be a contiguous (B, S, 2) int32 tensor on x's device")
+        noised, targets = torch.empty_like(x), torch.empty_like(x)
+        concat = torch.empty(b, 1 + c, tt, dtype=torch.float32, device=x.device)
+        self._chk(self.lib.sat_diffusion_noise_inpaint(_ptr(x), _ptr(noise), _ptr(t), _ptr(segments), _ptr(noised), _ptr(targets), _ptr(concat),
+                                                       b, c, tt, segments.shape[1], self.OBJECTIVES[objective], 1.0 / float(latent_scale),
+                                                       int(bool(mask_first)), self._stream(x)))
+        return noised, targets, concat
+
     def _mse_args(self, who, out, targets, mask):
         dt = self._dt(out)
         self._f32(targets)

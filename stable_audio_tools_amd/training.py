@@ -849,6 +849,59 @@ class GraphedTrainStep:
         return out
 
 
+INPAINT_CONCAT_IDS = ("inpaint_mask", "inpaint_masked_input")
+
+
+def random_inpaint_segments(lengths, seq_len, max_mask_segments=10, mask_type_probabilities=None):
+    """random_inpaint_mask (models/inpainting.py:11-97) as a table of intervals instead of a mask: a host int32 tensor (B, S, 2),
+    S = max(1, max_mask_segments), of half-open intervals [start, end) in which the inpainting mask is 0; unused rows have
+    start == end.  `lengths`: B host ints, the real (unpadded) latent frames of each item — the reference's
+    `(padding_mask == 1).sum().item()`, one host synchronisation per item there.  Python's `random` is consumed exactly as the
+    reference consumes it, per item: random.choices over (RANDOM_SEGMENTS, FULL_MASK, CAUSAL_MASK) with the weights (default
+    [0.1, 0.8, 0.1]); FULL_MASK is [0, seq_len), padding included; a real length of 0 leaves the item unmasked for the other two;
+    RANDOM_SEGMENTS draws randint(1, max_mask_segments), then per segment randint(1, max(1, real // n)) and randint(0, real - len)
+    (intervals may overlap); CAUSAL_MASK draws the kept prefix randint(0, real) and masks [prefix, real)."""
+    import random
+    if mask_type_probabilities is None:
+        mask_type_probabilities = [0.1, 0.8, 0.1]
+    else:
+        if len(mask_type_probabilities) != 3:
+            raise ValueError(f"mask_type_probabilities must have 3 elements, one for each MaskType. Got {len(mask_type_probabilities)}.")
+        if not torch.isclose(torch.tensor(sum(mask_type_probabilities)), torch.tensor(1.0)):
+            raise ValueError(f"mask_type_probabilities must sum to 1.0. Current sum: {sum(mask_type_probabilities)}")
+    slots = max(1, int(max_mask_segments))
+    table = []
+    for real in (int(n) for n in lengths):
+        rows = []
+        kind = random.choices([0, 1, 2], weights=mask_type_probabilities, k=1)[0]
+        if kind == 1:                                                   # FULL_MASK
+            rows.append((0, seq_len))
+        elif real == 0:
+            pass
+        elif kind == 0:                                                 # RANDOM_SEGMENTS
+            n = random.randint(1, max_mask_segments)
+            longest = max(1, real // n)
+            for _ in range(n):
+                length = random.randint(1, longest)
+                if real - length < 0:
+                    continue
+                start = random.randint(0, real - length)
+                rows.append((start, start + length))
+        else:                                                           # CAUSAL_MASK
+            prefix = random.randint(0, real)
+            if prefix < real:
+                rows.append((prefix, real))
+        table.append(rows + [(0, 0)] * (slots - len(rows)))
+    return torch.tensor(table, dtype=torch.int32).reshape(len(table), slots, 2)
+
+
+def expand_inpaint_segments(segments, seq_len):
+    """The (B, 1, seq_len) bool inpainting mask of an interval table (B, S, 2), on its device: False inside any interval."""
+    pos = torch.arange(seq_len, device=segments.device)[None, None, :]
+    inside = (pos >= segments[:, :, 0:1]) & (pos < segments[:, :, 1:2])
+    return ~inside.any(dim=1, keepdim=True)
+
+
 class DiTTrainStep:
     """One optimisation step of the conditioned DiT on (pre-encoded) latents, data-parallel over the default
     process group — restated from DiffusionCondTrainingWrapper.training_step
@@ -865,16 +918,34 @@ class DiTTrainStep:
     The step never synchronises with the host (the reference's `mse_loss[mask].mean()` does) and reduces nothing to a scalar through
     torch's multi-block reductions (ops.sum_all): noising / targets and the masked loss run on csrc/diffusion_step.hip
     (ops.diffusion_noise, functional.MaskedMSEFn); `ops.dit_step_fused = False` is the torch formulation of the same maths (A/B).
-    Not restated: inpainting_config, input_concat_cond (the oracle has no leg for them), log_loss_info."""
+
+    Inpainting (`diffusion_cond_inpaint`, :429-438): `inpainting_config` is the model config's `training.inpainting` dict.  The random
+    mask of models/inpainting.py:11-97 is drawn on the host in the reference's order (random_inpaint_segments) from real lengths that
+    never cost a synchronisation — `inpaint_lengths` (host ints), else a CPU `padding_mask` (row sums after the resize of :375), else
+    the full length; a device `padding_mask` without `inpaint_lengths` raises.  As in the reference the draw uses the padding mask
+    whether or not `mask_padding` keeps it for the loss (:353 versus :435).  The interval table goes to the device through a ring of
+    pinned host buffers and a non-blocking copy, and ONE launch (ops.diffusion_noise_inpaint) writes the noised input, the targets,
+    the mask channel and the masked input, concatenated in the order of `input_concat_ids`, the model's `input_concat_cond`.
+    A concat model that is not an inpainting model takes a caller-made `input_concat_cond` in __call__ instead.
+    `gradient_clip_val` > 0 is Lightning's clip by norm (train.py:160), applied after the gradient exchange and before AdamW.
+    Not restated: log_loss_info, gradient accumulation."""
 
     def __init__(self, model, lr=5e-5, betas=(0.9, 0.999), weight_decay=1e-3, cfg_dropout_prob=0.1, timestep_sampler="uniform",
                  use_ema=True, autocast_dtype=None, ops=None, ddp_mode="all_reduce", bucket_bytes=256 << 20, seed=0, ddp_overlap=True,
                  ddp_comm_dtype=None, ddp_single_rank=None, timestep_sampler_options=None, dist_shift=None, p_one_shot=0.0,
                  mask_padding=False, mask_padding_dropout=0.0, latent_scale=1.0, lr_scheduler=None,
-                 validation_timesteps=(0.1, 0.3, 0.5, 0.7, 0.9)):
+                 validation_timesteps=(0.1, 0.3, 0.5, 0.7, 0.9), inpainting_config=None, input_concat_ids=INPAINT_CONCAT_IDS,
+                 gradient_clip_val=0.0):
         import math
         if lr_scheduler is not None and lr_scheduler["type"] != "InverseLR":
             raise NotImplementedError("only the InverseLR scheduler is restated")
+        if sorted(input_concat_ids) != sorted(INPAINT_CONCAT_IDS):
+            raise ValueError(f"input_concat_ids must be {INPAINT_CONCAT_IDS} in either order, got {tuple(input_concat_ids)!r}")
+        self.inpainting_config = inpainting_config
+        self.inpaint_mask_kwargs = dict(inpainting_config.get("mask_kwargs", {})) if inpainting_config is not None else None
+        self.inpaint_mask_first = tuple(input_concat_ids)[0] == "inpaint_mask"
+        self.gradient_clip_val = float(gradient_clip_val)
+        self._seg_ring, self._seg_ev, self._seg_slot = [None] * 8, [None] * 8, 0
         self._math = math
         self.model = model
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -949,6 +1020,57 @@ class DiTTrainStep:
         targets = noise * alphas - latents * sigmas if self.objective == "v" else noise - latents
         return noised, targets
 
+    def _inpaint_lengths(self, inpaint_lengths, padding_mask, batch, length):
+        """The real latent frames per item as host ints, without asking the device: `inpaint_lengths`, else the row sums of a CPU
+        `padding_mask` (resized as :375 does), else `length` for every item."""
+        if inpaint_lengths is not None:
+            lengths = [int(n) for n in inpaint_lengths]
+            if len(lengths) != batch:
+                raise ValueError(f"inpaint_lengths holds {len(lengths)} lengths for a batch of {batch}")
+            return lengths
+        if padding_mask is None:
+            return [length] * batch
+        if padding_mask.device.type != "cpu":
+            raise ValueError("inpainting draws its masks on the host: with a padding_mask on the device pass inpaint_lengths= "
+                             "(host ints, the real latent frames per item)")
+        if padding_mask.shape[-1] != length:
+            padding_mask = torch.nn.functional.interpolate(padding_mask.unsqueeze(1).float(), size=length, mode="nearest").squeeze(1).bool()
+        return (padding_mask == 1).sum(dim=1).tolist()
+
+    def _segments_to_device(self, table, device):
+        """The drawn (B, S, 2) host table on `device`: staged in one of eight pinned buffers and copied without blocking (the event of
+        the copy that last read a slot is waited for before the slot is rewritten, as GraphedTrainStep's ring does)."""
+        if device.type == "cpu":
+            return table
+        slot = self._seg_slot
+        self._seg_slot = (slot + 1) % len(self._seg_ring)
+        if self._seg_ev[slot] is not None:
+            self._seg_ev[slot].synchronize()
+        host = self._seg_ring[slot]
+        if host is None or host.shape != table.shape:
+            host = self._seg_ring[slot] = torch.empty(table.shape, dtype=torch.int32).pin_memory()
+        host.copy_(table)
+        seg = torch.empty(table.shape, dtype=torch.int32, device=device)
+        seg.copy_(host, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._seg_ev[slot] = ev
+        return seg
+
+    def _inpaint_front(self, latents, noise, t, segments):
+        """(noised, targets, input_concat_cond) of :377-379, :406-420, :429-438 for a DEVICE interval table: one launch, or with
+        ops.dit_step_fused = False the same in torch ops (the table expanded, torch.where, cat)."""
+        ops = self._ops()
+        if ops.dit_step_fused:
+            return ops.diffusion_noise_inpaint(latents.float().contiguous(), noise.float().contiguous(), t.float().contiguous(),
+                                               segments.contiguous(), self.objective, self.latent_scale, self.inpaint_mask_first)
+        noised, targets = self._noise_targets(latents, noise, t)
+        keep = expand_inpaint_segments(segments, latents.shape[2])
+        scaled = latents / self.latent_scale if self.latent_scale != 1.0 else latents
+        masked = torch.where(keep, scaled.float(), torch.zeros((), dtype=torch.float32, device=latents.device))
+        parts = [keep.to(torch.float32), masked]
+        return noised, targets, torch.cat(parts if self.inpaint_mask_first else parts[::-1], dim=1)
+
     def _loss(self, out, targets, mask):
         """MSELoss(mask_key="padding_mask") (losses.py:76-89): the mean over the elements `mask` (B, T) selects, or over all of them."""
         ops = self._ops()
@@ -984,36 +1106,48 @@ class DiTTrainStep:
         return self.model(noised, t, **kw)
 
     def __call__(self, latents, cross_attn_cond=None, global_embed=None, t=None, noise=None, prepend_cond=None, padding_mask=None,
-                 use_padding_mask=None):
+                 use_padding_mask=None, input_concat_cond=None, inpaint_lengths=None):
+        if self.inpainting_config is not None and input_concat_cond is not None:
+            raise ValueError("input_concat_cond is made by the step when inpainting_config is set: pass one or the other")
         self.flat.zero_grad()
         mask = self._padding_mask(padding_mask, use_padding_mask, latents.shape[2])
+        if mask is not None and mask.device != latents.device:
+            mask = mask.to(latents.device)
         if t is None:
             t = self.draw_timesteps(latents.shape[0], latents.device, latents.shape[2])
         if noise is None:
             noise = torch.randn_like(latents)
-        noised, targets = self._noise_targets(latents, noise, t)
+        if self.inpainting_config is not None:
+            lengths = self._inpaint_lengths(inpaint_lengths, padding_mask, latents.shape[0], latents.shape[2])
+            table = random_inpaint_segments(lengths, latents.shape[2], **self.inpaint_mask_kwargs)
+            noised, targets, input_concat_cond = self._inpaint_front(latents, noise, t, self._segments_to_device(table, latents.device))
+        else:
+            noised, targets = self._noise_targets(latents, noise, t)
         out = self._model(noised, t, cross_attn_cond=cross_attn_cond, global_embed=global_embed, prepend_cond=prepend_cond,
-                          cfg_dropout_prob=self.cfg_dropout_prob, mask=mask)
+                          cfg_dropout_prob=self.cfg_dropout_prob, mask=mask, input_concat_cond=input_concat_cond)
         loss = self._loss(out, targets, mask)
         self.comm.mark_backward_start()
         loss.backward()
         self.comm.mark_backward_end()
         self.flat.gather_grads(self.opt._ops)
         self.comm()
+        if self.gradient_clip_val > 0.0:
+            clip_flat_grads(self.flat, self.gradient_clip_val, self.comm.grad_scale, self.opt._ops)
         self.opt.step(lr=self.current_lr(), grad_scale=self.comm.grad_scale)
         self.global_step += 1
         return {"loss": loss.detach()}
 
     @torch.no_grad()
-    def validation_losses(self, latents, cross_attn_cond=None, global_embed=None, prepend_cond=None, noise=None):
+    def validation_losses(self, latents, cross_attn_cond=None, global_embed=None, prepend_cond=None, noise=None, input_concat_cond=None):
         """validation_step (:533-564): for every entry of validation_timesteps the UNMASKED loss of the whole batch at that timestep, with
         fresh noise (or `noise`, one tensor for all timesteps) and cfg_dropout_prob = 0 — {"val/loss_0.1": 0-d tensor, ...}.  Parameters,
-        gradients and optimizer state are left alone."""
+        gradients and optimizer state are left alone.  The reference's validation_step draws no inpainting masks, so neither does this:
+        `input_concat_cond` is handed to the model as it is (an inpainting model needs the caller's own conditioning here)."""
         losses = {}
         for vt in self.validation_timesteps:
             t = torch.full((latents.shape[0],), vt, device=latents.device)
             noised, targets = self._noise_targets(latents, torch.randn_like(latents) if noise is None else noise, t)
             out = self._model(noised, t, cross_attn_cond=cross_attn_cond, global_embed=global_embed, prepend_cond=prepend_cond,
-                              cfg_dropout_prob=0.0)
+                              cfg_dropout_prob=0.0, input_concat_cond=input_concat_cond)
             losses[f"val/loss_{vt:.1f}"] = self._loss(out, targets, None)
         return losses
