@@ -603,6 +603,17 @@ int sat_cast_bf16_dual(const void* src, long long lds, void* dst, long long ldd,
 int sat_split_bf16x3(const float* src, long long lds, void* dst, long long ldd, int R, int C, int side, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Layout junction of the transformer autoencoder (csrc/layout.hip) — the Transpose modules around a TAAEBlock's
+ * transformer stack, models/autoencoders.py:85-89, :101, :117.  One launch each, no workspace, 64-bit offsets
+ * (B * C * T may pass 2^31), any C >= 1 and T >= 1 (16-byte accesses when C % 8 == 0, T % 4 == 0 and both bases are
+ * 16-byte aligned; a scalar edge path otherwise).
+ * sat_ct_to_tokens: x fp32 (B, C, T) -> y (B, T, C), fp32 or (out_bf16 = 1) bf16 rounded to nearest even as sat_cast_bf16.
+ * sat_tokens_to_ct: x (B, T, C) fp32 or (in_bf16 = 1) bf16 -> y fp32 (B, C, T).
+ * ---------------------------------------------------------------------------------------------- */
+int sat_ct_to_tokens(const float* x, void* y, int B, int C, int T, int out_bf16, void* stream);
+int sat_tokens_to_ct(const void* x, float* y, int B, int C, int T, int in_bf16, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DiT optimisation step, front and tail (csrc/diffusion_step.hip) — DiffusionCondTrainingWrapper.training_step,
  * training/diffusion.py:377-379, :406-420 (noising, targets) and MSELoss with a padding mask, training/losses/losses.py:76-89.
  * Replaces the torch elementwise chain, `mse_loss[mask].mean()` (a host sync) and their autograd.  No atomics: bit-reproducible.

@@ -130,6 +130,9 @@ SIGNATURES = {
     "sat_cast_bf16_tpair": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P, _L, _I, _I, _I, _I, _P]),
     "sat_cast_bf16_dual": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P]),
     "sat_split_bf16x3": (_I, [_P, _L, _P, _L, _I, _I, _I, _P]),
+    # layout.hip
+    "sat_ct_to_tokens": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "sat_tokens_to_ct": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     # dit_ops.hip
     "sat_layernorm_fwd": (_I, [_P] * 5 + [_L] + [_P] * 3 + [_I] * 3 + [_F, _I, _P]),
     "sat_layernorm_fwd_fp8": (_I, [_P] * 5 + [_L] + [_P] * 2 + [_I] * 3 + [_F, _I, _P]),

@@ -6,6 +6,8 @@ Mirrors (same class names, constructor kwargs, module tree and therefore state_d
     OobleckEncoder :285, OobleckDecoder :320, AudioAutoencoder :401 (encode :446, decode :493)
   stable_audio_tools/models/blocks.py  SnakeBeta :301
 so a reference checkpoint loads unchanged (weight_g / weight_v / bias / alpha / beta).
+Also the transformer autoencoder, inference only: Transpose :85, TAAEBlock :91, TAAEEncoder :158, TAAEDecoder :195 and the "taae"
+factory types (:813, :853) — the conv stack's (B, C, T) meets the transformer blocks' (B, N, D) tokens in csrc/layout.hip.
 
 What is different is the execution: the module tree is only a parameter container.  Forward walks
 it in *fusion units* (functional.py) so SnakeBeta, bias, residual add and tanh never make their own
@@ -21,6 +23,7 @@ from torch.nn.utils.weight_norm import WeightNorm as _TorchWeightNorm
 
 from . import functional as Fn
 from .bottleneck import VAEBottleneck  # noqa: F401  (re-export, mirrors reference import surface)
+from .transformer import TransformerBlock, _sliding_window
 
 
 class SnakeBeta(nn.Module):
@@ -355,6 +358,188 @@ class OobleckDecoder(nn.Module):
         return mods[-2](x, snake=mods[-3], tanh_out=self.final_tanh)
 
 
+class Transpose(nn.Module):
+    """The reference's Transpose (autoencoders.py:85-89): the first and last entry of a TAAEBlock's transformer list, kept so that the
+    blocks sit at the reference's indices (state-dict keys `...layers.<j>.<1 + i>.`).  TAAEBlock.forward does not call it: the layout
+    change is the junction kernel pair (ops.ct_to_tokens / ops.tokens_to_ct).  The standalone forward is a view."""
+
+    def forward(self, x, **kwargs):
+        return x.transpose(-1, -2)
+
+
+def _token_dtype(x, blocks):
+    """bf16 tokens under bf16 autocast (or for blocks stored in bf16), else fp32; fp16 is refused."""
+    dt = blocks[0].ff.ff[2].weight.dtype if blocks else torch.float32
+    if dt == torch.float16:
+        raise NotImplementedError("a TAAE in fp16 (AutoencoderPretransform(model_half=True)) is not built: the transformer blocks serve "
+                                  "fp32 and bf16 only — keep the model in fp32 and use torch.autocast(dtype=torch.bfloat16)")
+    dev = "cuda" if x.is_cuda else "cpu"
+    if torch.is_autocast_enabled(dev):
+        if torch.get_autocast_dtype(dev) != torch.bfloat16:
+            raise NotImplementedError("only bf16 autocast is on the HIP path (the TAAE transformer blocks serve fp32 and bf16 only)")
+        return torch.bfloat16
+    return torch.bfloat16 if dt == torch.bfloat16 else torch.float32
+
+
+class TAAEBlock(nn.Module):
+    """One stage of the transformer autoencoder (autoencoders.py:91-156): a strided weight-normed conv plus a stack of transformer
+    blocks (head dim 128, qk_norm "ln", a rotary table per block, LayerScale, LayerNorm eps 1e-2, biased SwiGLU feed-forward, sliding
+    window).  Encoder: [three ResidualUnits] [SnakeBeta] strided conv (Identity at stride 1), transformers; decoder: transformers,
+    [SnakeBeta] transposed conv (Identity at stride 1), [three ResidualUnits].  Same module tree and state-dict keys as the reference.
+    Execution: the SnakeBeta rides in the conv's prologue; the transformer stack runs on (B, T, C) tokens between ONE ops.ct_to_tokens
+    and ONE ops.tokens_to_ct (csrc/layout.hip), in bf16 under bf16 autocast, else fp32.  Inference only (head dim 128, the window and
+    the folded LayerScale have no backward); `checkpointing` is accepted and has nothing to do."""
+
+    def __init__(self, in_channels, out_channels, stride, type="encoder", transformer_depth=3, use_snake=False, sliding_window=[31, 32],
+                 checkpointing=False, conformer=False, layer_scale=True, use_dilated_conv=False):
+        super().__init__()
+        if type not in ("encoder", "decoder"):
+            raise ValueError(f"Unknown type {type}. Must be 'encoder' or 'decoder'")
+        if conformer:
+            raise NotImplementedError("TAAEBlock(conformer=True): there is no ConformerModule on the HIP path")
+        if use_dilated_conv and not use_snake:
+            raise NotImplementedError("TAAEBlock(use_dilated_conv=True, use_snake=False): the reference's ResidualUnit then uses ELU, which is "
+                                      "not built on the HIP path (only SnakeBeta is)")
+        if type == "decoder" and use_snake and in_channels != out_channels:
+            # the reference builds SnakeBeta(out_channels) in front of a conv whose input has in_channels (autoencoders.py:133): its forward
+            # fails on the shape mismatch.  There is no behaviour to reproduce, so the config is refused where it is built.
+            raise ValueError(f"TAAEBlock(type='decoder', use_snake=True) needs in_channels == out_channels (got {in_channels} and "
+                             f"{out_channels}): the reference's SnakeBeta there has out_channels parameters but acts on in_channels "
+                             "channels, and fails in forward")
+        _sliding_window(sliding_window)
+        self.type = type
+        self.checkpointing = checkpointing
+        self.sliding_window = sliding_window
+        self.use_snake, self.use_dilated_conv, self.stride = bool(use_snake), bool(use_dilated_conv), stride
+        transformer_dim = out_channels if type == "encoder" else in_channels
+        transformers = [Transpose()]
+        for _ in range(transformer_depth):
+            transformers.append(TransformerBlock(transformer_dim, dim_heads=128, causal=False, zero_init_branch_outputs=not layer_scale,
+                                                 remove_norms=False, conformer=False, layer_scale=layer_scale, add_rope=True,
+                                                 attn_kwargs={"qk_norm": "ln"}, ff_kwargs={"mult": 4, "no_bias": False},
+                                                 norm_kwargs={"eps": 1e-2}))
+        transformers.append(Transpose())
+        transformers = nn.ModuleList(transformers)
+
+        def units(c):
+            return [ResidualUnit(c, c, dilation=d, use_snake=use_snake) for d in (1, 3, 9)] if use_dilated_conv else []
+        pad = math.ceil(stride / 2)
+        if type == "encoder":
+            layers = units(in_channels)
+            layers.append(SnakeBeta(in_channels) if use_snake else nn.Identity())
+            layers.append(WNConv1d(in_channels, out_channels, kernel_size=2 * stride, stride=stride, padding=pad) if stride > 1 else nn.Identity())
+            layers.append(transformers)
+        else:
+            layers = [transformers]
+            layers.append(SnakeBeta(out_channels) if use_snake else nn.Identity())
+            layers.append(WNConvTranspose1d(in_channels, out_channels, kernel_size=2 * stride, stride=stride, padding=pad) if stride > 1 else nn.Identity())
+            layers += units(out_channels)
+        self.layers = nn.ModuleList(layers)
+
+    def _parts(self):
+        mods = list(self.layers)
+        n = 3 if self.use_dilated_conv else 0
+        if self.type == "encoder":
+            return mods[:n], mods[n], mods[n + 1], mods[n + 2]
+        return mods[3:], mods[1], mods[2], mods[0]
+
+    def _transformers(self, x, transformers):
+        ops = Fn._ops(None)
+        blocks = list(transformers)[1:-1]
+        dt = _token_dtype(x, blocks)
+        if not blocks:
+            return x
+        if ops.taae_junction_fused:
+            tok = ops.ct_to_tokens(x.contiguous(), dt)
+        else:
+            tok = x.transpose(1, 2).contiguous().to(dt)
+        for blk in blocks:
+            tok = blk(tok, self_attention_flash_sliding_window=self.sliding_window)
+        if ops.taae_junction_fused:
+            return ops.tokens_to_ct(tok.contiguous())
+        return tok.float().transpose(1, 2).contiguous()
+
+    @staticmethod
+    def _units(x, units):
+        for i, u in enumerate(units):
+            x = u(x, next_snake=units[i + 1].entry_snake() if i + 1 < len(units) else None)
+        return x
+
+    def _conv(self, x, act, conv):
+        snake = act if self.use_snake else None
+        if isinstance(conv, nn.Identity):
+            return act(x) if snake is not None else x
+        return conv(x, snake=snake)
+
+    def forward(self, x):
+        if torch.is_grad_enabled():
+            raise NotImplementedError("the transformer autoencoder (TAAE) is inference-only (head dim 128 attention, the sliding window and the "
+                                      "folded LayerScale have no backward kernels): run the model under torch.no_grad()")
+        units, act, conv, transformers = self._parts()
+        if self.type == "encoder":
+            return self._transformers(self._conv(self._units(x, units), act, conv), transformers)
+        return self._units(self._conv(self._transformers(x, transformers), act, conv), units)
+
+
+def _taae_dims(channels, c_mults):
+    dims = [c * channels for c in c_mults]
+    return [dims[0]] + dims
+
+
+class TAAEEncoder(nn.Module):
+    """autoencoders.py:158-193: k7 conv, one encoder TAAEBlock per stride, [SnakeBeta], k3 conv to the latent."""
+
+    def __init__(self, in_channels=2, channels=128, latent_dim=32, c_mults=[1, 2, 4, 8], strides=[2, 4, 8, 8], transformer_depths=[3, 3, 3, 3],
+                 use_snake=False, sliding_window=[63, 64], checkpointing=False, conformer=False, layer_scale=True, use_dilated_conv=False,
+                 **kwargs):
+        super().__init__()
+        dims = _taae_dims(channels, c_mults)
+        self.depth = len(c_mults)
+        self.use_snake = bool(use_snake)
+        layers = [WNConv1d(in_channels, dims[0], kernel_size=7, padding=3, bias=True)]
+        for i in range(self.depth):
+            layers += [TAAEBlock(dims[i], dims[i + 1], stride=strides[i], transformer_depth=transformer_depths[i], use_snake=use_snake,
+                                 sliding_window=sliding_window, checkpointing=checkpointing, conformer=conformer, layer_scale=layer_scale,
+                                 use_dilated_conv=use_dilated_conv, **kwargs)]
+        layers += [SnakeBeta(dims[-1]) if use_snake else nn.Identity(),
+                   WNConv1d(dims[-1], latent_dim, kernel_size=3, padding=1, bias=True)]
+        self.layers = nn.Sequential(*layers)
+
+    def forward(self, x):
+        mods = list(self.layers)
+        x = mods[0](x)
+        for blk in mods[1:-2]:
+            x = blk(x)
+        return mods[-1](x, snake=mods[-2] if self.use_snake else None)
+
+
+class TAAEDecoder(nn.Module):
+    """autoencoders.py:195-231: k3 conv from the latent, one decoder TAAEBlock per stride, [SnakeBeta], k7 conv without bias (no tanh)."""
+
+    def __init__(self, out_channels=2, channels=128, latent_dim=32, c_mults=[1, 2, 4, 8], strides=[2, 4, 8, 8], transformer_depths=[3, 3, 3, 3],
+                 use_snake=False, sliding_window=[63, 64], checkpointing=False, conformer=False, layer_scale=True, use_dilated_conv=False,
+                 **kwargs):
+        super().__init__()
+        dims = _taae_dims(channels, c_mults)
+        self.depth = len(c_mults)
+        self.use_snake = bool(use_snake)
+        layers = [WNConv1d(latent_dim, dims[-1], kernel_size=3, padding=1, bias=True)]
+        for i in range(self.depth, 0, -1):
+            layers += [TAAEBlock(dims[i], dims[i - 1], stride=strides[i - 1], type="decoder", transformer_depth=transformer_depths[i - 1],
+                                 use_snake=use_snake, sliding_window=sliding_window, checkpointing=checkpointing, conformer=conformer,
+                                 layer_scale=layer_scale, use_dilated_conv=use_dilated_conv, **kwargs)]
+        layers += [SnakeBeta(dims[0]) if use_snake else nn.Identity(),
+                   WNConv1d(dims[0], out_channels, kernel_size=7, padding=3, bias=False)]
+        self.layers = nn.Sequential(*layers)
+
+    def forward(self, x):
+        mods = list(self.layers)
+        x = mods[0](x)
+        for blk in mods[1:-2]:
+            x = blk(x)
+        return mods[-1](x, snake=mods[-2] if self.use_snake else None)
+
+
 class AudioAutoencoder(nn.Module):
     """Encoder / bottleneck / decoder orchestration (autoencoders.py:401-534, :601-732).
     Inner `pretransform` (wavelet/PQMF front-ends) is out of scope and must be None."""
@@ -483,10 +668,14 @@ def _chunk_windows(total, chunk, overlap):
     return wins
 
 
+_ENCODERS = {"oobleck": OobleckEncoder, "taae": TAAEEncoder}
+_DECODERS = {"oobleck": OobleckDecoder, "taae": TAAEDecoder}
+
+
 def create_encoder_from_config(cfg):
-    if cfg.get("type") != "oobleck":
-        raise NotImplementedError(f"encoder type {cfg.get('type')!r} is out of scope (only 'oobleck' is on the hot path)")
-    enc = OobleckEncoder(**cfg["config"])
+    if cfg.get("type") not in _ENCODERS:
+        raise NotImplementedError(f"encoder type {cfg.get('type')!r} is out of scope (only 'oobleck' and 'taae' are on the hot path)")
+    enc = _ENCODERS[cfg["type"]](**cfg["config"])
     if not cfg.get("requires_grad", True):
         for p in enc.parameters():
             p.requires_grad = False
@@ -494,9 +683,9 @@ def create_encoder_from_config(cfg):
 
 
 def create_decoder_from_config(cfg):
-    if cfg.get("type") != "oobleck":
-        raise NotImplementedError(f"decoder type {cfg.get('type')!r} is out of scope (only 'oobleck' is on the hot path)")
-    dec = OobleckDecoder(**cfg["config"])
+    if cfg.get("type") not in _DECODERS:
+        raise NotImplementedError(f"decoder type {cfg.get('type')!r} is out of scope (only 'oobleck' and 'taae' are on the hot path)")
+    dec = _DECODERS[cfg["type"]](**cfg["config"])
     if not cfg.get("requires_grad", True):
         for p in dec.parameters():
             p.requires_grad = False

@@ -343,10 +343,39 @@ class Linear(nn.Module):
         w = self.weight
         return self._cache.get(w, "bf16", lambda: _pad_rows8(w.detach() if w.dtype == torch.bfloat16 else _ops().cast_bf16(w.detach())))
 
-    def forward(self, x, res=None, mode=None):
-        """mode None: x W^T + b [+ res];  'swiglu': value * silu(gate) over W rows = [value | gate]."""
+    def scaled(self, scale):
+        """(weight, bias, cache) of this projection with a per-output-channel `scale` folded in — rows of the weight and the bias times
+        scale, in fp32 — for y = scale * (x W^T + b) at the cost of x W^T + b (transformer.LayerScale).  A derived weight in the
+        projection's cache: valid for one (storage, version, epoch) of the weight, the bias AND the scale, so an in-place change of
+        any of them is seen; `cache` holds the low-precision / split copies made from the folded weight."""
+        w, b = self.weight, self.bias
+
+        def make():
+            s = scale.detach().float()
+            return (w.detach().float() * s[:, None]).contiguous(), (b.detach().float() * s if b is not None else None), _WeightCache()
+        srcs = (w, scale) + ((b,) if b is not None else ())
+        if not _caches.trackable(*srcs):
+            return make()
+        key = tuple((t.data_ptr(), _caches.version_of(t), t.dtype, t.device) for t in srcs) + (_caches.epoch_of(*srcs),)
+        hit = self._cache.items.get("scaled")
+        if hit is None or hit[0] != key:
+            hit = (key, make())
+            self._cache.items["scaled"] = hit
+        return hit[1]
+
+    def forward(self, x, res=None, mode=None, out_scale=None):
+        """mode None: x W^T + b [+ res];  'swiglu': value * silu(gate) over W rows = [value | gate].
+        out_scale: (out_features,) per-channel scale of the result before `res` is added: out_scale * (x W^T + b) [+ res], folded into
+        the weight (scaled()); inference only — the scale gets no gradient."""
         if mode is None:
             mode = "res" if res is not None else "plain"
+        if out_scale is not None:
+            if torch.is_grad_enabled():
+                raise NotImplementedError("Linear(out_scale=...) is inference-only (the folded scale has no gradient): run under torch.no_grad()")
+            if isinstance(x, Fp8Rows) or mode == "swiglu" or out_scale.shape != (self.out_features,):
+                raise NotImplementedError("Linear(out_scale=...): a (out_features,) scale on a plain or residual projection of a tensor input")
+            w, b, cache = self.scaled(out_scale)
+            return LinearFn.apply(x, w, b, res, mode, _lowp(x, self.weight), cache, self.fp8)
         if isinstance(x, Fp8Rows):
             return self._forward_fp8_rows(x, res, mode)
         return LinearFn.apply(x, self.weight, self.bias, res, mode, _lowp(x, self.weight), self._cache, self.fp8)

@@ -1720,6 +1720,33 @@ class SatOps:
         self._chk(self.lib.sat_split_bf16x3(_ptr(src), src.stride(0), _ptr(dst), 3 * c, r, c, side, self._stream(src)))
         return dst
 
+    # ------------------------------------------------------------------ TAAE layout junction (csrc/layout.hip)
+    # autoencoders.TAAEBlock enters and leaves its transformer stack through ct_to_tokens / tokens_to_ct.  False: torch's
+    # x.transpose(1, 2).contiguous() plus a cast, the same values bit for bit (A/B runs: tools/taae_bench.py --ops-set taae_junction_fused=0)
+    taae_junction_fused = True
+
+    def ct_to_tokens(self, x, dtype=torch.float32):
+        """x fp32 (B, C, T) contiguous -> (B, T, C) tokens in `dtype` (float32, or bfloat16 rounded to nearest even): sat_ct_to_tokens."""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"ct_to_tokens: tokens are float32 or bfloat16, got {dtype}")
+        if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+            raise ValueError("ct_to_tokens takes a non-empty contiguous float32 (B, C, T) tensor")
+        self._f32(x)
+        b, c, t = x.shape
+        y = torch.empty(b, t, c, dtype=dtype, device=x.device)
+        self._chk(self.lib.sat_ct_to_tokens(_ptr(x), _ptr(y), b, c, t, int(dtype == torch.bfloat16), self._stream(x)))
+        return y
+
+    def tokens_to_ct(self, x):
+        """x (B, T, C) contiguous tokens, float32 or bfloat16 -> fp32 (B, C, T): sat_tokens_to_ct."""
+        if x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous() or x.numel() == 0:
+            raise ValueError("tokens_to_ct takes a non-empty contiguous float32 or bfloat16 (B, T, C) tensor")
+        self._dt(x)
+        b, t, c = x.shape
+        y = torch.empty(b, c, t, dtype=torch.float32, device=x.device)
+        self._chk(self.lib.sat_tokens_to_ct(_ptr(x), _ptr(y), b, c, t, int(x.dtype == torch.bfloat16), self._stream(x)))
+        return y
+
     # ------------------------------------------------------------------ DiT train step: noising, masked loss (csrc/diffusion_step.hip)
     # training.DiTTrainStep forms noised inputs / targets and the (padding-masked) MSE on these kernels.  False: the torch formulation of
     # the same maths, torch.where + functional.sum_all for the masked mean (A/B: bench.py --ops-set dit_step_fused=0)

@@ -14,9 +14,13 @@ residual work of the block fused into the GEMM epilogues — no library GEMM.  A
 sat_qk_norm_fwd / sat_qk_norm_bwd kernels in training and fp32.  ContinuousTransformer(sliding_window=[left, right])
 (flash-attn's window_size on every layer's self-attention, transformer.py:436, :845) runs on the windowed forward
 kernel (sat_attention_fwd_window) in inference, fp32 and bf16, head dims 64 and 128; training with a window, a
-window on cross-attention and a window over an fp8 input projection raise NotImplementedError.  So do the options
-of the reference that the Stable Audio DiT configs never enable (qk_norm="dyt", differential attention, conformer,
-layer_scale, memory tokens, causal, flex-attention masks, abs/sinusoidal position embeddings).
+window on cross-attention and a window over an fp8 input projection raise NotImplementedError.
+TransformerBlock(layer_scale=True) (LayerScale :243, x = x + scale * branch(...), :684-712) is inference-only: the scale is folded into
+the rows of each branch's output projection (a derived weight, cached per version of weight and scale), so it costs no launch;
+TransformerBlock(add_rope=True) (:656, :672-673) gives the block a rotary table of its own, forward and backward.  These two, head dim
+128, qk_norm "ln" and the window are the block of the transformer autoencoder (autoencoders.TAAEBlock).  The options of the reference
+that no supported config enables raise NotImplementedError (qk_norm="dyt", differential attention, conformer, memory tokens, causal,
+flex-attention masks, abs/sinusoidal position embeddings).
 
 Forward AND backward run on the HIP kernels: every fused operator is a torch.autograd.Function whose
 backward calls the matching kernel (LayerNorm+adaLN, rotary transpose, attention dQ / dK,dV with
@@ -463,9 +467,10 @@ class FeedForward(nn.Module):
                 nn.init.zeros_(linear_out.bias)
         self.ff = nn.Sequential(linear_in, nn.Identity(), linear_out, nn.Identity())
 
-    def forward(self, x, res=None):
-        """res: the residual stream — added in the output projection's epilogue (x = x + ff(...), transformer.py:711)."""
-        return self.ff[2](self.ff[0](x), res=res)
+    def forward(self, x, res=None, out_scale=None):
+        """res: the residual stream — added in the output projection's epilogue (x = x + ff(...), transformer.py:711).
+        out_scale: a LayerScale's parameter, folded into the output projection's rows and bias (Linear.forward; inference only)."""
+        return self.ff[2](self.ff[0](x), res=res, out_scale=out_scale)
 
 
 def _sliding_window(window):
@@ -546,7 +551,7 @@ class Attention(nn.Module):
             return ops.gemm_heads_fp8(qx, qw, alpha, cs, heads, nb, ntok, sec0, nsec, reuse=tag, col_alpha=calpha)
         return ops.gemm_heads_bf16(x2, lin.lowp_weight(), cs, heads, nb, ntok, sec0, nsec, reuse=tag)
 
-    def _forward_hd128(self, x, kv_input, rotary_pos_emb, res, norm, window=None):
+    def _forward_hd128(self, x, kv_input, rotary_pos_emb, res, norm, window=None, out_scale=None):
         """Head dim 128 (inference only; fp32 and bf16): projection through the Linear, then the standalone norm + rotary kernel
         (sat_qk_norm_fwd_hd) or the in-place rotary, then plane preparation and the forward kernel of csrc/attention.hip at D = 128
         (ops.attention), then to_out with the residual epilogue.  The projection-epilogue fusion of the head dim 64 bf16 path
@@ -590,12 +595,14 @@ class Attention(nn.Module):
             q = qk[..., :hd].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
             k = qk[..., hd:].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
             v = qkv[..., 2 * hd:].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
-        return self.to_out(ops.attention(q, k, v, self.scale, window=window), res=res)
+        return self.to_out(ops.attention(q, k, v, self.scale, window=window), res=res, out_scale=out_scale)
 
-    def forward(self, x, context=None, rotary_pos_emb=None, causal=None, res=None, flash_attn_sliding_window=None, **unsupported):
+    def forward(self, x, context=None, rotary_pos_emb=None, causal=None, res=None, flash_attn_sliding_window=None, out_scale=None,
+                **unsupported):
         """res: the residual stream, added in the output projection's epilogue (x = x + attn(...), transformer.py:703-707).
         flash_attn_sliding_window: (left, right), flash-attn's window_size (transformer.py:436) — self-attention under torch.no_grad()
-        only; applied always (the reference drops it with a warning where the flash-attn package is missing, transformer.py:414-415)."""
+        only; applied always (the reference drops it with a warning where the flash-attn package is missing, transformer.py:414-415).
+        out_scale: a LayerScale's parameter, folded into to_out's rows (Linear.forward; inference only)."""
         for k, v in unsupported.items():
             if v is not None:
                 raise NotImplementedError(f"Attention.forward({k}=...) is not on the HIP path")
@@ -620,9 +627,9 @@ class Attention(nn.Module):
                 raise NotImplementedError("a sliding window on an fp8 input projection is not built (keep to_qkv in bf16)")
             window = _ops().attn_window(window, n, n)      # None when it hides nothing at this length: the dense paths, bit for bit
         if dh == 128:
-            return self._forward_hd128(x, kv_input, rotary_pos_emb, res, norm, window)
+            return self._forward_hd128(x, kv_input, rotary_pos_emb, res, norm, window, out_scale)
         if window is not None and not (_lowp(x, first.weight) and first.lowp_weight() is not None):
-            return self._forward_hd128(x, kv_input, rotary_pos_emb, res, norm, window)      # fp32: the standalone kernels, at head dim 64
+            return self._forward_hd128(x, kv_input, rotary_pos_emb, res, norm, window, out_scale)      # fp32: the standalone kernels, at head dim 64
         if not torch.is_grad_enabled() and _lowp(x, first.weight) and first.lowp_weight() is not None \
                 and (not cross or self.to_kv.lowp_weight() is not None):
             # inference, bf16: head split, rotary and the attention kernel's operand planes come straight out of the
@@ -662,14 +669,14 @@ class Attention(nn.Module):
                 cs = rotary_pos_emb[0] if rotary_pos_emb is not None else None
                 pl = self._heads(ops, self.to_qkv, x2, cs, h, b, n, 0, 3, "self", norm)
                 out = ops.attention_planes(pl["q"], pl["k"], pl["v_tr"], n, n, self.scale, window=window)
-            return self.to_out(out, res=res)
+            return self.to_out(out, res=res, out_scale=out_scale)
         if _ops().train_fused_nodes and dh == 64:
             if cross:
                 out = _CrossAttnFn.apply(self.to_q(x), self.to_kv(kv_input), h, kv_h, dh, self.scale, norm, *self._norm_params())
             else:
                 cs = rotary_pos_emb[0] if rotary_pos_emb is not None else None
                 out = _SelfAttnFn.apply(self.to_qkv(x), cs, h, dh, self.scale, norm, *self._norm_params())     # (B, N, H*dh): heads already merged
-            return self.to_out(out, res=res)
+            return self.to_out(out, res=res, out_scale=out_scale)
         if cross:
             q2 = self.to_q(x)
             kv = self.to_kv(kv_input)
@@ -691,7 +698,20 @@ class Attention(nn.Module):
             k = qkv[..., hd:2 * hd].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
             v = qkv[..., 2 * hd:].unflatten(-1, (h, dh)).permute(0, 2, 1, 3)
         out = _AttentionCoreFn.apply(q, k, v, self.scale)       # (B, N, H*dh): heads already merged
-        return self.to_out(out, res=res)
+        return self.to_out(out, res=res, out_scale=out_scale)
+
+
+class LayerScale(nn.Module):
+    """The per-channel scale of a residual branch (transformer.py:243-248): one parameter `scale`, 1e-5 at construction.  Standalone
+    forward for API parity; inside TransformerBlock the multiply never runs — the scale is folded into the branch's output projection
+    (Linear.forward(out_scale=...)), inference only."""
+
+    def __init__(self, dim, init_val=1e-5):
+        super().__init__()
+        self.scale = nn.Parameter(torch.full([dim], init_val))
+
+    def forward(self, x):
+        return x * self.scale
 
 
 def _fp8_rows_for(attn, lin):
@@ -705,24 +725,57 @@ class TransformerBlock(nn.Module):
                  zero_init_branch_outputs=True, conformer=False, layer_ix=-1, remove_norms=False, add_rope=False,
                  layer_scale=False, attn_kwargs={}, ff_kwargs={}, norm_kwargs={}):
         super().__init__()
-        if conformer or remove_norms or add_rope or layer_scale or causal:
-            raise NotImplementedError("conformer / remove_norms / add_rope / layer_scale / causal are not on the HIP path")
+        if conformer or remove_norms or causal:
+            raise NotImplementedError("conformer / remove_norms / causal are not on the HIP path")
         self.dim = dim
         self.dim_heads = min(dim_heads, dim)
         self.cross_attend = cross_attend
         self.dim_context = dim_context
+        if layer_scale:      # the scales start at 1e-5: zero-initialised branches on top would be redundant (transformer.py:609-611)
+            zero_init_branch_outputs = False
+        self.layer_scale = bool(layer_scale)
+        self.add_rope = bool(add_rope)
         self.pre_norm = LayerNorm(dim, **norm_kwargs)
         self.self_attn = Attention(dim, dim_heads=self.dim_heads, zero_init_output=zero_init_branch_outputs, **attn_kwargs)
+        self.self_attn_scale = LayerScale(dim) if layer_scale else nn.Identity()
         if cross_attend:
             self.cross_attend_norm = LayerNorm(dim, **norm_kwargs)
             self.cross_attn = Attention(dim, dim_heads=self.dim_heads, dim_context=dim_context,
                                         zero_init_output=zero_init_branch_outputs, **attn_kwargs)
+            self.cross_attn_scale = LayerScale(dim) if layer_scale else nn.Identity()
         self.ff_norm = LayerNorm(dim, **norm_kwargs)
         self.ff = FeedForward(dim, zero_init_output=zero_init_branch_outputs, **ff_kwargs)
+        self.ff_scale = LayerScale(dim) if layer_scale else nn.Identity()
         self.layer_ix = layer_ix
         self.global_cond_dim = global_cond_dim
         if global_cond_dim is not None:
             self.to_scale_shift_gate = nn.Parameter(torch.randn(6 * dim) / dim ** 0.5)
+        # a rotary table of the block's own (transformer.py:656), used when the caller hands none in (:672-673)
+        self.rope = RotaryEmbedding(self.dim_heads // 2) if add_rope else None
+
+    def _forward_layer_scale(self, x, context, global_cond, rotary_pos_emb, sw):
+        """layer_scale=True, inference: x = x + scale * branch(...) (transformer.py:704-712), under adaLN x = branch * sigmoid(1 - gate) *
+        scale + x (:684-686, :699-701).  The scale is folded into each branch's output projection (Linear.forward(out_scale=...)), so
+        the block runs the launches of the block without it: the residual add stays in the GEMM epilogue, the gate in _GateResidualFn."""
+        if torch.is_grad_enabled():
+            raise NotImplementedError("TransformerBlock(layer_scale=True) is inference-only (the scale is folded into the output projections and "
+                                      "has no gradient): run the model under torch.no_grad()")
+        d = self.dim
+        s_attn, s_ff = self.self_attn_scale.scale, self.ff_scale.scale
+        if self.global_cond_dim is not None and self.global_cond_dim > 0 and global_cond is not None:
+            mod = (self.to_scale_shift_gate + global_cond).to(x.dtype).contiguous()   # (B, 6D)
+            scale_self, shift_self, gate_self = mod[:, 0:d], mod[:, d:2 * d], mod[:, 2 * d:3 * d]
+            scale_ff, shift_ff, gate_ff = mod[:, 3 * d:4 * d], mod[:, 4 * d:5 * d], mod[:, 5 * d:6 * d]
+            h = self.self_attn(self.pre_norm(x, scale_self, shift_self), rotary_pos_emb=rotary_pos_emb, flash_attn_sliding_window=sw, out_scale=s_attn)
+            x = _GateResidualFn.apply(h, gate_self, x)
+            if context is not None and self.cross_attend:
+                x = self.cross_attn(self.cross_attend_norm(x), context=context, res=x, out_scale=self.cross_attn_scale.scale)
+            h = self.ff(self.ff_norm(x, scale_ff, shift_ff), out_scale=s_ff)
+            return _GateResidualFn.apply(h, gate_ff, x)
+        x = self.self_attn(self.pre_norm(x), rotary_pos_emb=rotary_pos_emb, res=x, flash_attn_sliding_window=sw, out_scale=s_attn)
+        if context is not None and self.cross_attend:
+            x = self.cross_attn(self.cross_attend_norm(x), context=context, res=x, out_scale=self.cross_attn_scale.scale)
+        return self.ff(self.ff_norm(x), res=x, out_scale=s_ff)
 
     def forward(self, x, context=None, global_cond=None, rotary_pos_emb=None, self_attention_flash_sliding_window=None, **unsupported):
         """self_attention_flash_sliding_window: (left, right) for self_attn alone (transformer.py:683, :704; inference only);
@@ -732,6 +785,10 @@ class TransformerBlock(nn.Module):
                 raise NotImplementedError(f"TransformerBlock.forward({k}=...) is not on the HIP path")
         d = self.dim
         sw = self_attention_flash_sliding_window
+        if rotary_pos_emb is None and self.add_rope:
+            rotary_pos_emb = self.rope.forward_from_seq_len(x.shape[-2])
+        if self.layer_scale:
+            return self._forward_layer_scale(x, context, global_cond, rotary_pos_emb, sw)
         if self.global_cond_dim is not None and self.global_cond_dim > 0 and global_cond is not None:
             # adaLN: (to_scale_shift_gate + global_cond).chunk(6)   (transformer.py:677)
             # cast to the activation dtype: under bf16 autocast the fp32 parameter promotes the sum to fp32 while x is bf16
