@@ -614,6 +614,23 @@ int sat_ct_to_tokens(const float* x, void* y, int B, int C, int T, int out_bf16,
 int sat_tokens_to_ct(const void* x, float* y, int B, int C, int T, int in_bf16, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dithered-FSQ bottleneck, eval mode (csrc/fsq.hip) — DitheredFSQ.forward / indices_to_codes, models/fsq.py:64-134, as
+ * DitheredFSQBottleneck.encode / decode_tokens use them (models/bottleneck.py:426-484).  One launch each, no workspace, no
+ * device upload, capturable in a HIP graph, 64-bit offsets.  levels (D ints), half_l (D floats, 2 / (L_d - 1) in fp32) and
+ * table (the D tables arange(L_d) * half_l[d] - 1 concatenated, sum(L_d) floats) are HOST arrays computed by torch: they
+ * travel in the kernel arguments.  Channel q * D + d is digit d of codebook q; C == D * Q.
+ * Refused before any launch: L_d < 2, D > 16, sum(L_d) > 512, prod(L_d) > 2^63 - 1, C != D * Q, B, C or T < 1.
+ * sat_fsq_encode: x fp32 (B, C, T) -> codes fp32 (B, C, T) = table[d][r], r = rint((tanh(x) + 1) / half_l[d]) clamped to
+ *   [0, L_d - 1], and indices int64 (B, T, Q) = sum_d r_d * basis[d], basis = cumprod([1] + levels[:-1]).
+ * sat_fsq_decode_tokens: tokens int64 (B, T, Q), any value -> codes fp32 (B, C, T), digit d = floor(token / basis[d]) mod L_d
+ *   (floor division, non-negative remainder).
+ * ---------------------------------------------------------------------------------------------- */
+int sat_fsq_encode(const float* x, float* codes, long long* indices, int B, int C, int T, int D, int Q,
+                   const int* levels, const float* half_l, const float* table, void* stream);
+int sat_fsq_decode_tokens(const long long* tokens, float* codes, int B, int C, int T, int D, int Q,
+                          const int* levels, const float* table, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DiT optimisation step, front and tail (csrc/diffusion_step.hip) — DiffusionCondTrainingWrapper.training_step,
  * training/diffusion.py:377-379, :406-420 (noising, targets) and MSELoss with a padding mask, training/losses/losses.py:76-89.
  * Replaces the torch elementwise chain, `mse_loss[mask].mean()` (a host sync) and their autograd.  No atomics: bit-reproducible.

@@ -133,6 +133,9 @@ SIGNATURES = {
     # layout.hip
     "sat_ct_to_tokens": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "sat_tokens_to_ct": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    # fsq.hip
+    "sat_fsq_encode": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "sat_fsq_decode_tokens": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     # dit_ops.hip
     "sat_layernorm_fwd": (_I, [_P] * 5 + [_L] + [_P] * 3 + [_I] * 3 + [_F, _I, _P]),
     "sat_layernorm_fwd_fp8": (_I, [_P] * 5 + [_L] + [_P] * 2 + [_I] * 3 + [_F, _I, _P]),

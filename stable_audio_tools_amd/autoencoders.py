@@ -22,7 +22,7 @@ from torch import nn
 from torch.nn.utils.weight_norm import WeightNorm as _TorchWeightNorm
 
 from . import functional as Fn
-from .bottleneck import VAEBottleneck  # noqa: F401  (re-export, mirrors reference import surface)
+from .bottleneck import DiscreteBottleneck, DitheredFSQBottleneck, VAEBottleneck  # noqa: F401  (re-export, mirrors reference import surface)
 from .transformer import TransformerBlock, _sliding_window
 
 
@@ -588,6 +588,13 @@ class AudioAutoencoder(nn.Module):
             decoded = torch.tanh(decoded)
         return decoded
 
+    def decode_tokens(self, tokens, **kwargs):
+        """Token ids to audio, discrete autoencoders only (autoencoders.py:536-546).  The bottleneck hands back (B, C, T) latents —
+        bottleneck.DitheredFSQBottleneck.decode_tokens says where that departs from the reference."""
+        assert isinstance(self.bottleneck, DiscreteBottleneck), "decode_tokens only works with discrete autoencoders"
+        latents = self.bottleneck.decode_tokens(tokens, **kwargs)
+        return self.decode(latents, **kwargs)
+
     # -- chunked overlap-and-paste orchestration (autoencoders.py:601-732) --------------------
     def encode_audio(self, audio, chunked=False, overlap=32, chunk_size=128, **kwargs):
         """`overlap` / `chunk_size` are in latent frames (autoencoders.py:601-669)."""
@@ -692,6 +699,17 @@ def create_decoder_from_config(cfg):
     return dec
 
 
+def create_bottleneck_from_config(cfg):
+    """models/factory.py:89-154 for the bottlenecks on the HIP path: "vae", and "dithered_fsq" for inference."""
+    kind = cfg.get("type", None)
+    assert kind is not None, "type must be specified in bottleneck config"
+    if kind == "vae":
+        return VAEBottleneck()
+    if kind == "dithered_fsq":
+        return DitheredFSQBottleneck(**cfg["config"])
+    raise NotImplementedError(f"bottleneck type {kind!r} is out of scope (only 'vae' and 'dithered_fsq' are on the hot path)")
+
+
 def create_autoencoder_from_config(config):
     """Same JSON surface as autoencoders.py:867-910 for the in-scope types."""
     ae = config["model"]
@@ -701,9 +719,7 @@ def create_autoencoder_from_config(config):
     decoder = create_decoder_from_config(ae["decoder"])
     bottleneck = None
     if ae.get("bottleneck") is not None:
-        if ae["bottleneck"]["type"] != "vae":
-            raise NotImplementedError("only the 'vae' bottleneck is on the hot path")
-        bottleneck = VAEBottleneck()
+        bottleneck = create_bottleneck_from_config(ae["bottleneck"])
     return AudioAutoencoder(encoder, decoder, latent_dim=ae["latent_dim"], downsampling_ratio=ae["downsampling_ratio"],
                             sample_rate=config["sample_rate"], io_channels=ae["io_channels"], bottleneck=bottleneck,
                             in_channels=ae.get("in_channels"), out_channels=ae.get("out_channels"),

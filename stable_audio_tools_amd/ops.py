@@ -1747,6 +1747,66 @@ class SatOps:
         self._chk(self.lib.sat_tokens_to_ct(_ptr(x), _ptr(y), b, c, t, int(x.dtype == torch.bfloat16), self._stream(x)))
         return y
 
+    # ------------------------------------------------------------------ dithered-FSQ bottleneck, eval mode (csrc/fsq.hip)
+    _fsq_cache = {}     # levels tuple -> host tables; a function of the levels alone, shared by every SatOps
+
+    @classmethod
+    def _fsq_tables(cls, who, levels):
+        """The host arrays sat_fsq_* take, cached per levels tuple: levels (int32), half_l = 1.0 * 2 / (levels - 1) and the D tables
+        arange(L_d) * half_l[d] - 1 concatenated, both computed by torch in fp32 exactly as models/fsq.py:57 / :82-84 compute them (a
+        multiply and a subtract, two roundings), plus D and the codebook size.  The limits are those of the C entry points."""
+        key = tuple(int(v) for v in levels)
+        if key not in cls._fsq_cache:
+            if not 1 <= len(key) <= 16:
+                raise ValueError(f"{who}: 1 to 16 levels per codebook, got {len(key)}")
+            if min(key) < 2:
+                raise ValueError(f"{who}: every level count is >= 2, got {list(key)}")
+            if sum(key) > 512:
+                raise ValueError(f"{who}: the level counts sum to {sum(key)}, more than the 512 table entries a launch carries")
+            size = 1
+            for v in key:
+                size *= v
+            if size > 2 ** 63 - 1:
+                raise ValueError(f"{who}: the codebook size (the product of the levels) passes 2^63 - 1")
+            half_l = 1.0 * 2 / (torch.tensor(key, dtype=torch.int64) - 1)
+            assert half_l.dtype == torch.float32
+            table = torch.cat([torch.arange(v, dtype=torch.float32) * half_l[d] - 1.0 for d, v in enumerate(key)])
+            cls._fsq_cache[key] = (torch.tensor(key, dtype=torch.int32), half_l.contiguous(), table.contiguous(), len(key), size)
+        return cls._fsq_cache[key]
+
+    def fsq_encode(self, x, levels, num_codebooks=1):
+        """x fp32 (B, C, T) contiguous, C = len(levels) * num_codebooks -> (codes fp32 (B, C, T), indices int64 (B, T, Q)): the eval-mode
+        DitheredFSQ of the reference on the conv stack's layout, one launch (sat_fsq_encode)."""
+        if not torch.is_tensor(x) or x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+            raise ValueError("fsq_encode takes a non-empty contiguous float32 (B, C, T) tensor")
+        lv, half_l, table, d, _ = self._fsq_tables("fsq_encode", levels)
+        b, c, t = x.shape
+        q = int(num_codebooks)
+        if q < 1 or c != d * q:
+            raise ValueError(f"fsq_encode: {c} channels are not {d} levels x {q} codebooks")
+        self._f32(x)
+        codes = torch.empty_like(x)
+        indices = torch.empty(b, t, q, dtype=torch.int64, device=x.device)
+        self._chk(self.lib.sat_fsq_encode(_ptr(x), _ptr(codes), _ptr(indices), b, c, t, d, q, _ptr(lv), _ptr(half_l), _ptr(table),
+                                          self._stream(x)))
+        return codes, indices
+
+    def fsq_decode_tokens(self, tokens, levels):
+        """tokens (B, T, Q) contiguous, int64 (other integer dtypes are converted, as the reference's .to(torch.int64)) -> codes fp32
+        (B, Q * len(levels), T): DitheredFSQ.indices_to_codes on the conv stack's layout, one launch (sat_fsq_decode_tokens).  Any int64
+        value decodes as the reference decodes it: floor division and a non-negative modulo."""
+        if (not torch.is_tensor(tokens) or tokens.dim() != 3 or tokens.is_floating_point() or tokens.is_complex() or tokens.dtype == torch.bool
+                or not tokens.is_contiguous() or tokens.numel() == 0):
+            raise ValueError("fsq_decode_tokens takes a non-empty contiguous integer (B, T, Q) tensor")
+        lv, _, table, d, _ = self._fsq_tables("fsq_decode_tokens", levels)
+        if not self.simulator and not tokens.is_cuda:
+            raise RuntimeError("stable_audio_tools_amd kernels need CUDA(HIP) tensors; there is no CPU path")
+        tokens = tokens.to(torch.int64)
+        b, t, q = tokens.shape
+        codes = torch.empty(b, d * q, t, dtype=torch.float32, device=tokens.device)
+        self._chk(self.lib.sat_fsq_decode_tokens(_ptr(tokens), _ptr(codes), b, d * q, t, d, q, _ptr(lv), _ptr(table), self._stream(tokens)))
+        return codes
+
     # ------------------------------------------------------------------ DiT train step: noising, masked loss (csrc/diffusion_step.hip)
     # training.DiTTrainStep forms noised inputs / targets and the (padding-masked) MSE on these kernels.  False: the torch formulation of
     # the same maths, torch.where + functional.sum_all for the masked mean (A/B: bench.py --ops-set dit_step_fused=0)

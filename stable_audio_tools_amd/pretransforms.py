@@ -47,8 +47,8 @@ class AutoencoderPretransform(Pretransform):
         self.iterate_batch = iterate_batch
         self.encoded_channels = model.latent_dim
         self.chunked = chunked
-        self.num_quantizers = None
-        self.codebook_size = None
+        self.num_quantizers = model.bottleneck.num_quantizers if self.is_discrete else None
+        self.codebook_size = model.bottleneck.codebook_size if self.is_discrete else None
         if self.model_half:
             self.model.half()
 
@@ -70,10 +70,13 @@ class AutoencoderPretransform(Pretransform):
         return decoded
 
     def tokenize(self, x, **kwargs):
-        raise AssertionError("Cannot tokenize with a continuous model")
+        assert self.model.is_discrete, "Cannot tokenize with a continuous model"
+        _, info = self.model.encode(x, return_info=True, **kwargs)
+        return info[self.model.bottleneck.tokens_id]
 
     def decode_tokens(self, tokens, **kwargs):
-        raise AssertionError("Cannot decode tokens with a continuous model")
+        assert self.model.is_discrete, "Cannot decode tokens with a continuous model"
+        return self.model.decode_tokens(tokens, **kwargs)
 
     def load_state_dict(self, state_dict, strict=True):
         return self.model.load_state_dict(state_dict, strict=strict)
