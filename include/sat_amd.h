@@ -155,6 +155,34 @@ int sat_conv1d_bf16x3_planesq(const short* xp_hi, const short* xp_lo, int rows, 
                              float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int dil, int pad, int tanh_out,
                              int flags, void* stream);      /* flags bit 0: one workgroup per tile instead of the persistent launch (A/B); bit 1: persistent at any size (tests) */
 int sat_convtr1d_bf16x3_partial_rows(int B, int Tout, int stride, int pad);
+/* Split over input-channel chunks ("split-K") for the three conv entry points above: a launch of few tiles and a long K loop leaves most
+ * CUs idle, so n workgroups per tile each run 1/n of the chunks and store their raw accumulators to a workspace slab; a second launch of
+ * the same kernel (one workgroup per tile, empty chunk range) sums the slabs in index order and runs the ordinary epilogue — no atomics, the
+ * same bits every run.
+ *   sat_conv_split_rule(tiles, nchunks, resident, cus)  THE rule: min(cus * resident / tiles, nchunks / 8) splits (>= 8 chunks each), evened out;
+ *                          1 = do not split.  resident = workgroups per CU of the plan (2; 3 for k = 1; 1 for the planes kernel).
+ *   sat_conv_bf16x3_split  the split count of one call — kind 0 = sat_conv1d_bf16x3, 1 = sat_convtr1d_bf16x3, 2 = sat_conv1d_bf16x3_planesq; split =
+ *                          -1 the rule | 0 off | n >= 2 forced; cus <= 0: this device's CU count — and the floats of workspace it takes
+ *                          (*ws_floats, may be NULL).  -1: shape not served, or a forced count the launch cannot have.  Host code only.
+ *   the _ws entry points   the plain ones (sat_conv1d_bf16x3_ws: sat_conv1d_bf16x3_emit with em_hi = NULL allowed) + ws (16-byte aligned, at least
+ *                          the floats sat_conv_bf16x3_split reports, owned by the caller until both launches have run) + split as above.  A forced
+ *                          count the launch cannot have is status 1 and no launch.  The plain entry points never split. */
+int sat_conv_split_rule(int tiles, int nchunks, int resident, int cus);
+int sat_conv_bf16x3_split(int kind, int B, int Cin, int Cout, int Tout, int K, int stride, int dil, int pad, int split, int cus,
+                          long long* ws_floats);
+int sat_conv1d_bf16x3_ws(const float* x, const short* w_hi, const short* w_lo, const float* bias, const float* snake_a,
+                         const float* snake_ib, const float* res, float* y, const float* x2, const float* alpha2,
+                         const float* beta2, float* part_da, float* part_db, int B, int Cin, int Cout, int Tin, int Tout,
+                         int K, int stride, int dil, int pad, int tanh_out, void* em_hi, void* em_lo,
+                         const float* em_a, const float* em_ib, int em_rows, float* ws, long long ws_floats, int split, void* stream);
+int sat_convtr1d_bf16x3_ws(const float* x, const short* w_hi, const short* w_lo, const float* bias, const float* snake_a,
+                           const float* snake_ib, const float* res, float* y, const float* x2, const float* alpha2,
+                           const float* beta2, float* part_da, float* part_db, int B, int Cin, int Cout, int Tin, int Tout,
+                           int K, int stride, int pad, int tanh_out, float* ws, long long ws_floats, int split, void* stream);
+int sat_conv1d_bf16x3_planesq_ws(const short* xp_hi, const short* xp_lo, int rows, const short* w_hi, const short* w_lo, const float* bias,
+                                 const float* res, float* y, const float* x2, const float* alpha2, const float* beta2, float* part_da,
+                                 float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int dil, int pad, int tanh_out,
+                                 int flags, float* ws, long long ws_floats, int split, void* stream);
 int sat_pack_weights_bf16x3(const float* w, short* hi, short* lo, int D0, int D1, int K, int stride, int mode, void* stream);
 long long sat_pack_weights_bf16x3_size(int D0, int D1, int K, int stride, int mode);
 int sat_snake_consts(const float* alpha, const float* beta, float* a, float* ib, int C, void* stream);

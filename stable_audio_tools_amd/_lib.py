@@ -47,6 +47,11 @@ SIGNATURES = {
     "sat_residual_unit_fwd": (_I, [_P, _P, _I] + [_P] * 11 + [_I] * 6 + [_P] * 4 + [_I, _P]),
     "sat_pack_weights_k7q_size": (_L, [_I, _I, _I, _I]),
     "sat_convtr1d_bf16x3_partial_rows": (_I, [_I] * 4),
+    "sat_conv_split_rule": (_I, [_I] * 4),
+    "sat_conv_bf16x3_split": (_I, [_I] * 11 + [_P]),
+    "sat_conv1d_bf16x3_ws": (_I, [_P] * 13 + [_I] * 10 + [_P] * 4 + [_I, _P, _L, _I, _P]),
+    "sat_convtr1d_bf16x3_ws": (_I, [_P] * 13 + [_I] * 9 + [_P, _L, _I, _P]),
+    "sat_conv1d_bf16x3_planesq_ws": (_I, [_P, _P, _I] + [_P] * 10 + [_I] * 10 + [_P, _L, _I, _P]),
     "sat_pack_weights_bf16x3": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sat_pack_weights_bf16x3_size": (_L, [_I, _I, _I, _I, _I]),
     "sat_snake_consts": (_I, [_P, _P, _P, _P, _I, _P]),

@@ -16,6 +16,11 @@
 //     split are applied once per element while staging.
 //   * weights are pre-split and pre-arranged by sat_pack_weights_bf16x3 as [chunk][co][group][8],
 //     so a chunk's slab is a straight 16-byte-per-lane copy into padded LDS rows.
+//   * launches of few tiles and many chunks (the bottom of the U: 128 workgroups of 256 chunks, 8 of 128, the planes kernel's 4 of 128) are SPLIT
+//     over chunks (SatConvBfLaunch::nsplit / cps / ws, sat_conv_split_rule below): n workgroups per tile run 1 / n of the K loop each and store
+//     their raw accumulators to a workspace slab; a second launch of the SAME kernel with an empty chunk range sums a tile's slabs in index
+//     order and runs the unchanged epilogue (one copy of it, no atomics, the same bits every run).  730 -> 333 + 27 us, 261 -> 24 + 31 us and
+//     278 -> ~24 + 30 us per launch on the flagship step (profiles/conv_split/README.md).
 #include "conv_common.h"
 #include <type_traits>
 
@@ -59,7 +64,57 @@ struct SatConvBfLaunch {
     const float* ru_a2 = nullptr;
     const float* ru_ib2 = nullptr;
     float* ru_h = nullptr;
+    // split over input-channel chunks ("split-K", sat_conv_split_rule): launches whose tiles leave most CUs idle under a long K loop.
+    //   split launch  (nsplit >= 2, cps > 0):  nsplit workgroups per tile; workgroup (tile, z) runs the K loop over chunks [z * cps, min((z + 1) * cps,
+    //                 nchunks)), stores its RAW accumulators to slab (tile, z) of `ws` and returns — no epilogue;
+    //   finish launch (nsplit >= 2, cps == 0): one workgroup per tile, EMPTY chunk range: the accumulators start as slab 0 + slab 1 + ... (index
+    //                 order: the same bits every run) and fall through into the ordinary epilogue.
+    // nsplit <= 1: the plain launch.
+    int nsplit = 0;
+    int cps = 0;           // chunks per split
+    float* ws = nullptr;   // tiles x nsplit slabs of SAT_SPLIT_SLAB(waves) floats, 16-byte aligned
 };
+
+// A slab holds one workgroup's accumulators as [wave][mi][ni][quad][lane] float4 (quad q = accumulator registers 4q .. 4q + 3): every store and
+// load instruction of a wave moves 1 KiB of consecutive addresses, and a lane of the finish launch reads back exactly what the lane of the same
+// index wrote (the layout is private to these two functions).  Waves / accumulator rows that multiply nothing (channels past Cout) are skipped
+// on both sides by the same tile-derived flags.
+#define SAT_SPLIT_SLAB(nwaves) ((nwaves) * 4 * 16 * 64)
+template <int NW>
+SAT_DEVICE f32x4* sat_split_slab(float* ws, int tile, int z, int nsplit, int wave, int lane) {
+    return reinterpret_cast<f32x4*>(ws + ((size_t)tile * nsplit + z) * SAT_SPLIT_SLAB(NW) + (size_t)wave * (4 * 16 * 64)) + lane;
+}
+template <int NW>
+SAT_DEVICE void sat_split_store(float* ws, int tile, int z, int nsplit, int wave, int lane, const f32x16 (&acc)[2][2], bool mi1_on) {
+    f32x4* s = sat_split_slab<NW>(ws, tile, z, nsplit, wave, lane);
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+        if (mi == 1 && !mi1_on) break;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                s[((mi * 2 + ni) * 4 + q) * 64] = f32x4{acc[mi][ni][4 * q], acc[mi][ni][4 * q + 1], acc[mi][ni][4 * q + 2], acc[mi][ni][4 * q + 3]};
+    }
+}
+template <int NW>
+SAT_DEVICE void sat_split_sum(const float* ws, int tile, int nsplit, int wave, int lane, f32x16 (&acc)[2][2], bool mi1_on) {
+    for (int z = 0; z < nsplit; ++z) {                    // (acc is zero on entry; index order: the sum's bits do not depend on which split finished first)
+        const f32x4* s = sat_split_slab<NW>(const_cast<float*>(ws), tile, z, nsplit, wave, lane);
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+            if (mi == 1 && !mi1_on) break;
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 v = s[((mi * 2 + ni) * 4 + q) * 64];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[mi][ni][4 * q + j] += v[j];
+                }
+        }
+    }
+}
 
 #include "conv_epilogue.h"        // the output epilogue of this file's kernel and of the k7 / k7q ones
 
@@ -108,8 +163,18 @@ sat_conv1d_bf16x3_kernel(SatConvBfLaunch a) {
     const int lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     // grid = (time tiles, channel tiles, B): the channel tiles of one activation window share an XCD (sat_xcd_tile)
+    // (split launch: grid z = B x nsplit — split z_s of every tile, then split z_s + 1 of every tile)
     int co_tile, win;
-    sat_xcd_tile(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), gridDim.y, gridDim.x * gridDim.z, &co_tile, &win);
+    int tile_lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+    const bool split_on = a.nsplit > 1;                   // block-uniform (kernel argument)
+    const bool split_fin = split_on && a.cps == 0;
+    int z_s = 0;
+    if (split_on) {
+        const int tiles = (int)(gridDim.x * gridDim.y) * p.B;
+        z_s = tile_lin / tiles;
+        tile_lin -= z_s * tiles;
+    }
+    sat_xcd_tile(tile_lin, gridDim.y, (int)gridDim.x * p.B, &co_tile, &win);
     const int b = win / (int)gridDim.x, t_tile = win - b * (int)gridDim.x;
     const int t0 = t_tile * SAT_T_T;
     const int co0 = co_tile * SAT_CO_T;
@@ -152,6 +217,11 @@ sat_conv1d_bf16x3_kernel(SatConvBfLaunch a) {
     __syncthreads();                                       // (the first write_lds reads the table)
 
     const int nchunks = (a.cin_v + 8 * CS - 1) / (8 * CS);
+    // this workgroup's chunk range [c_lo, c_hi): everything (plain launch), split z_s's share, or nothing (finish launch: the slabs' sum instead).
+    // No chunk at or past c_hi is ever requested.
+    const int c_lo = split_on ? z_s * a.cps : 0;
+    const int c_hi = split_on ? (c_lo + a.cps < nchunks ? c_lo + a.cps : nchunks) : nchunks;
+    if (split_fin && wave_on) sat_split_sum<4>(a.ws, tile_lin, a.nsplit, wave, lane, acc, mi1_on);
     // Register-staged software pipeline: the global loads of chunk c+1 are issued right after the barrier that
     // publishes chunk c, so their HBM/L2 latency runs under chunk c's MFMA phase; they are converted and written
     // to LDS after the phase's closing barrier.
@@ -303,42 +373,49 @@ sat_conv1d_bf16x3_kernel(SatConvBfLaunch a) {
     };
     using SatSet0 = std::integral_constant<int, 0>;
     using SatSet1 = std::integral_constant<int, NSET - 1>;
-    issue_loads(0, SatSet0{});
-    issue_w(0);
+    if (c_lo < c_hi) {
+        issue_loads(c_lo, SatSet0{});
+        issue_w(c_lo);
+    }
     if constexpr (DEEP) {
-        if (nchunks > 1) issue_loads(1, SatSet1{});
-        for (int c = 0; c < nchunks; c += 2) {
+        if (c_lo + 1 < c_hi) issue_loads(c_lo + 1, SatSet1{});
+        for (int c = c_lo; c < c_hi; c += 2) {
             write_lds(c, SatSet0{});
             __syncthreads();
             // (oldest first: vmcnt retires in order — the weights of chunk c + 1 are needed one phase before the activations of c + 2)
-            if (c + 1 < nchunks) issue_w(c + 1);
+            if (c + 1 < c_hi) issue_w(c + 1);
             SAT_SCHED_FENCE();                             // (the scheduler would otherwise mix the two groups: program order IS the retire order)
-            if (c + 2 < nchunks) issue_loads(c + 2, SatSet0{});
+            if (c + 2 < c_hi) issue_loads(c + 2, SatSet0{});
             SAT_SCHED_FENCE();
             mfma_chunk();
             __syncthreads();
-            if (c + 1 < nchunks) {                         // (block-uniform)
+            if (c + 1 < c_hi) {                         // (block-uniform)
                 write_lds(c + 1, SatSet1{});
                 __syncthreads();
-                if (c + 2 < nchunks) issue_w(c + 2);
+                if (c + 2 < c_hi) issue_w(c + 2);
                 SAT_SCHED_FENCE();
-                if (c + 3 < nchunks) issue_loads(c + 3, SatSet1{});
+                if (c + 3 < c_hi) issue_loads(c + 3, SatSet1{});
                 SAT_SCHED_FENCE();
                 mfma_chunk();
                 __syncthreads();
             }
         }
     } else {
-        for (int c = 0; c < nchunks; ++c) {
+        for (int c = c_lo; c < c_hi; ++c) {
             write_lds(c, SatSet0{});
             __syncthreads();
-            if (c + 1 < nchunks) {
+            if (c + 1 < c_hi) {
                 issue_loads(c + 1, SatSet0{});
                 issue_w(c + 1);
             }
             mfma_chunk();
             __syncthreads();
         }
+    }
+
+    if (split_on && !split_fin) {                          // split launch: the raw accumulators to this split's slab, no epilogue
+        if (wave_on) sat_split_store<4>(a.ws, tile_lin, z_s, a.nsplit, wave, lane, acc, mi1_on);
+        return;
     }
 
     // ------------- epilogue (as conv1d.hip; virtual channel m = co*S + r lands on y[co][q*S + r - out_shift]) -------------
@@ -601,9 +678,80 @@ extern "C" int sat_snake_consts(const float* alpha, const float* beta, float* a,
 #include "conv1d_planes.h"        // activation planes [B][Cin/8][rows][8] (pre-pass kernel; layout constants)
 #include "conv1d_bf16x3_k7q.h"    // planes, 16-channel chunks (one tap per MFMA k-step), two wave rows one barrier apart
 
-static int sat_bf_launch(const char* what, SatConvBfLaunch& a, const SatBfPlan& pl, void* stream) {
+// ------------------------------------------------------------------------------------------------
+// Split over input-channel chunks.  A launch of few tiles and a long K loop runs on a small part of the chip (the bottom of the U at T = 1024: a
+// 1024 -> 2048 stride-8 conv is 128 workgroups of 256 chunks each on 256 CUs; the 2048 -> 64 k7 data-gradient is FOUR workgroups of 128 chunks).
+// THE RULE (one function, no per-shape table): as many splits as there are free workgroup slots per tile, while every split keeps at least
+// SAT_SPLIT_MINC chunks — below that its prologue (the first chunk's latency, uncovered) and the round trip of its slab are not amortised:
+//     nsplit = min(slots / tiles, nchunks / SAT_SPLIT_MINC),   slots = CUs x resident workgroups per CU of the plan,
+// evened out so that no split is empty (chunks per split = ceil(nchunks / nsplit), nsplit = ceil(nchunks / cps)); 1 = do not split.
+// ------------------------------------------------------------------------------------------------
+#define SAT_SPLIT_MINC 8
+#define SAT_SPLIT_MAX 64
+extern "C" int sat_conv_split_rule(int tiles, int nchunks, int resident, int cus) {
+    if (tiles <= 0 || nchunks <= 0 || resident <= 0 || cus <= 0) return 1;
+    const long long by_slots = (long long)cus * resident / tiles;
+    long long n = nchunks / SAT_SPLIT_MINC;
+    if (by_slots < n) n = by_slots;
+    if (n > SAT_SPLIT_MAX) n = SAT_SPLIT_MAX;
+    if (n < 2) return 1;
+    const int cps = sat_cdiv(nchunks, (int)n);
+    return sat_cdiv(nchunks, cps);
+}
+// what the rule looks at, for one launch: (0 tiles: a kernel that does not split — the direct k7 kernel, the fused unit)
+struct SatSplitGeom { int tiles, nchunks, resident, slab; };
+static SatSplitGeom sat_bf_split_geom(const SatConvBfLaunch& a, const SatBfPlan& pl) {
     if (pl.ng == 8 && pl.cs == 1 && a.sin_log2 == 0 && a.sout_log2 == 0) {
-        if (a.xp_hi && a.wq) sat_bf_launch_k7q(a, stream);
+        if (!(a.xp_hi && a.wq) || a.ru_w1_hi) return SatSplitGeom{0, 0, 0, 0};
+        return SatSplitGeom{(a.cout_pad / SAT_K7_CO) * sat_cdiv(a.nq, SAT_K7_T) * a.p.B, sat_cdiv(a.cin_v, 16), 1, SAT_SPLIT_SLAB(SAT_K7_NT / 64)};
+    }
+    return SatSplitGeom{sat_cdiv(a.nq, SAT_T_T) * (a.cout_pad / SAT_CO_T) * a.p.B, sat_cdiv(a.cin_v, 8 * pl.cs), pl.ng == 4 ? 3 : 2, SAT_SPLIT_SLAB(4)};
+}
+// want: < 0 the rule, 0 no split, n >= 2 exactly n splits.  Returns the split count (1: none), or -1 for a forced count the launch cannot have
+// (a kernel that does not split, more splits than chunks, or a count that would leave a split without chunks).  *ws_floats: the slabs' size.
+static int sat_bf_split_decide(const SatConvBfLaunch& a, const SatBfPlan& pl, int want, int cus, int* cps, long long* ws_floats) {
+    const SatSplitGeom g = sat_bf_split_geom(a, pl);
+    int n = 1;
+    *cps = 0;
+    *ws_floats = 0;
+    if (want == 0 || want == 1) return 1;
+    if (want < 0) {
+        if (g.tiles == 0) return 1;
+        n = sat_conv_split_rule(g.tiles, g.nchunks, g.resident, cus > 0 ? cus : sat_cu_count());
+        if (n < 2) return 1;
+    } else {
+        if (g.tiles == 0 || want > SAT_SPLIT_MAX || want > g.nchunks) return -1;
+        if (sat_cdiv(g.nchunks, sat_cdiv(g.nchunks, want)) != want) return -1;
+        n = want;
+    }
+    *cps = sat_cdiv(g.nchunks, n);
+    *ws_floats = (long long)g.tiles * n * g.slab;
+    return n;
+}
+// the split state of one call through a _ws entry point (the plain entry points: no workspace, no split)
+struct SatSplitWs { float* ws; long long ws_floats; int want; int cus; };
+static const SatSplitWs SAT_NO_SPLIT{nullptr, 0, 0, 0};
+
+static int sat_bf_launch_one(const char* what, SatConvBfLaunch& a, const SatBfPlan& pl, void* stream);
+static int sat_bf_launch(const char* what, SatConvBfLaunch& a, const SatBfPlan& pl, void* stream, const SatSplitWs& sw = SAT_NO_SPLIT) {
+    int cps;
+    long long need;
+    const int n = sat_bf_split_decide(a, pl, sw.want, sw.cus, &cps, &need);
+    if (n < 0) { sat_set_error("conv1d_bf16x3: this launch cannot be split that many ways (2 <= n <= chunks, every split at least one chunk; the direct k7 kernel and the fused unit do not split)"); return 1; }
+    if (n < 2) return sat_bf_launch_one(what, a, pl, stream);
+    if (!sw.ws || sw.ws_floats < need || ((uintptr_t)sw.ws & 15)) { sat_set_error("conv1d_bf16x3: the split workspace is missing, misaligned or smaller than sat_conv_bf16x3_split asks for"); return 1; }
+    a.ws = sw.ws;
+    a.nsplit = n;
+    a.cps = cps;                                           // split launch: n workgroups per tile
+    if (const int st = sat_bf_launch_one(what, a, pl, stream)) return st;
+    a.cps = 0;                                             // finish launch: the slabs' sum and the epilogue
+    return sat_bf_launch_one(what, a, pl, stream);
+}
+
+static int sat_bf_launch_one(const char* what, SatConvBfLaunch& a, const SatBfPlan& pl, void* stream) {
+    const unsigned zmul = (a.nsplit > 1 && a.cps > 0) ? (unsigned)a.nsplit : 1u;      // workgroups per tile
+    if (pl.ng == 8 && pl.cs == 1 && a.sin_log2 == 0 && a.sout_log2 == 0) {
+        if (a.xp_hi && a.wq) sat_bf_launch_k7q(a, stream, zmul);
         else sat_bf_launch_k7(a, stream);
         return sat_check_launch(what);
     }
@@ -613,7 +761,7 @@ static int sat_bf_launch(const char* what, SatConvBfLaunch& a, const SatBfPlan& 
         sat_set_error("conv1d_bf16x3: an activated input of more than 2048 channels (1024 for K <= 4 at stride 1) is not served by the bf16x3 kernels (ops.use_bf16x3 = False takes the fp32-MFMA ones)");
         return 1;
     }
-    dim3 grid(sat_cdiv(a.nq, SAT_T_T), a.cout_pad / SAT_CO_T, a.p.B);
+    dim3 grid(sat_cdiv(a.nq, SAT_T_T), a.cout_pad / SAT_CO_T, a.p.B * zmul);
     if (a.sin_log2 > 0) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 4, true>), grid, dim3(256), stream, a); }     // strided: always plan (8, 4)
     else if (pl.ng == 8 && pl.cs == 1) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 1, false>), grid, dim3(256), stream, a); }
     else if (pl.ng == 8 && pl.cs == 2) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 2, false>), grid, dim3(256), stream, a); }
@@ -630,7 +778,7 @@ static int sat_conv1d_bf16x3_impl(const char* what, const float* x, const short*
                                   const float* x2, const float* alpha2, const float* beta2, float* part_da,
                                   float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil,
                                   int pad, int tanh_out, short* em_hi, short* em_lo, const float* em_a, const float* em_ib, int em_rows,
-                                  void* stream) {
+                                  void* stream, const SatSplitWs& sw = SAT_NO_SPLIT, SatConvBfLaunch* geom_only = nullptr, SatBfPlan* plan_out = nullptr) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || Tin <= 0 || Tout <= 0) { sat_set_error("sat_conv1d_bf16x3: empty shape"); return 1; }
     SatBfPlan pl;
     if (!sat_bf_plan(K, stride, 0, &pl) || dil < 1 || (stride > 1 && dil != 1)) {
@@ -664,7 +812,8 @@ static int sat_conv1d_bf16x3_impl(const char* what, const float* x, const short*
         }
         a.em_hi = em_hi; a.em_lo = em_lo; a.em_a = em_a; a.em_ib = em_ib; a.em_rows = em_rows; a.em_c8 = sat_cdiv(Cout, 8);
     }
-    return sat_bf_launch(what, a, pl, stream);
+    if (geom_only) { *geom_only = a; *plan_out = pl; return 0; }     // (sat_conv_bf16x3_split: the launch's geometry, nothing enqueued)
+    return sat_bf_launch(what, a, pl, stream, sw);
 }
 extern "C" int sat_conv1d_bf16x3(const float* x, const short* w_hi, const short* w_lo, const float* bias,
                                  const float* snake_a, const float* snake_ib, const float* res, float* y,
@@ -689,6 +838,20 @@ extern "C" int sat_conv1d_bf16x3_emit(const float* x, const short* w_hi, const s
                                   B, Cin, Cout, Tin, Tout, K, stride, dil, pad, tanh_out, (short*)em_hi, (short*)em_lo, em_a, em_ib, em_rows, stream);
 }
 
+// sat_conv1d_bf16x3 / _emit (em_hi NULL: no emission) that may SPLIT its launch over input-channel chunks (sat_conv_split_rule): ws = a workspace of
+// ws_floats floats, at least what sat_conv_bf16x3_split(0, ...) reports for the same `split` (-1: the rule, 0: off, n >= 2: exactly n — status 1
+// and no launch where the launch cannot be split that way).  The workspace is written by the first launch and read by the second.
+extern "C" int sat_conv1d_bf16x3_ws(const float* x, const short* w_hi, const short* w_lo, const float* bias,
+                                    const float* snake_a, const float* snake_ib, const float* res, float* y,
+                                    const float* x2, const float* alpha2, const float* beta2, float* part_da,
+                                    float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil,
+                                    int pad, int tanh_out, void* em_hi, void* em_lo, const float* em_a, const float* em_ib, int em_rows,
+                                    float* ws, long long ws_floats, int split, void* stream) {
+    return sat_conv1d_bf16x3_impl("sat_conv1d_bf16x3_ws", x, w_hi, w_lo, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
+                                  B, Cin, Cout, Tin, Tout, K, stride, dil, pad, tanh_out, (short*)em_hi, (short*)em_lo, em_a, em_ib, em_rows, stream,
+                                  SatSplitWs{ws, ws_floats, split, 0});
+}
+
 // ---- the k = 5..7 stride-1 convs from pre-split activation planes (conv1d_planes.h, conv1d_bf16x3_k7q.h) ----
 // rows of one (batch, 8-channel chunk) plane: 32 zero rows, the sequence, zero rows up to the last window's halo
 extern "C" int sat_conv1d_k7_plane_rows(int Tin, int Tout, int pad) {
@@ -708,10 +871,11 @@ extern "C" int sat_conv1d_k7_planes(const float* x, const float* snake_a, const 
 }
 // sat_conv1d_bf16x3 for stride 1, 5 <= K <= 7, with the (activated) input given as planes (sat_conv1d_k7_planes or a producer's emission)
 // and the weights packed by sat_pack_weights_k7q (mode 0, or mode 1 for a data-gradient): conv1d_bf16x3_k7q.h.
-extern "C" int sat_conv1d_bf16x3_planesq(const short* xp_hi, const short* xp_lo, int rows, const short* w_hi, const short* w_lo,
-                                         const float* bias, const float* res, float* y, const float* x2, const float* alpha2,
-                                         const float* beta2, float* part_da, float* part_db, int B, int Cin, int Cout, int Tin, int Tout,
-                                         int K, int dil, int pad, int tanh_out, int flags, void* stream) {
+static int sat_conv1d_bf16x3_planesq_impl(const char* what, const short* xp_hi, const short* xp_lo, int rows, const short* w_hi, const short* w_lo,
+                                          const float* bias, const float* res, float* y, const float* x2, const float* alpha2,
+                                          const float* beta2, float* part_da, float* part_db, int B, int Cin, int Cout, int Tin, int Tout,
+                                          int K, int dil, int pad, int tanh_out, int flags, void* stream, const SatSplitWs& sw = SAT_NO_SPLIT,
+                                          SatConvBfLaunch* geom_only = nullptr) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || Tin <= 0 || Tout <= 0) { sat_set_error("sat_conv1d_bf16x3_planesq: empty shape"); return 1; }
     if (K < 5 || K > SAT_K7Q_TAPS || dil < 1 || (K - 1) * dil > 62) {
         sat_set_error("sat_conv1d_bf16x3_planesq: needs stride 1, 5 <= K <= 7, (K-1)*dil <= 62");
@@ -741,7 +905,24 @@ extern "C" int sat_conv1d_bf16x3_planesq(const short* xp_hi, const short* xp_lo,
     a.persist = (flags & 1) ? 0 : ((flags & 2) ? 2 : 1);      // flags bit 0: one workgroup per tile (round 5's launch; A/B runs and the tests'
                                                               // second arm); bit 1: persistent at any size (the tests: small shapes)
     SatBfPlan pl{8, 1, K};
-    return sat_bf_launch("sat_conv1d_bf16x3_planesq", a, pl, stream);
+    if (geom_only) { *geom_only = a; return 0; }
+    return sat_bf_launch(what, a, pl, stream, sw);
+}
+extern "C" int sat_conv1d_bf16x3_planesq(const short* xp_hi, const short* xp_lo, int rows, const short* w_hi, const short* w_lo,
+                                         const float* bias, const float* res, float* y, const float* x2, const float* alpha2,
+                                         const float* beta2, float* part_da, float* part_db, int B, int Cin, int Cout, int Tin, int Tout,
+                                         int K, int dil, int pad, int tanh_out, int flags, void* stream) {
+    return sat_conv1d_bf16x3_planesq_impl("sat_conv1d_bf16x3_planesq", xp_hi, xp_lo, rows, w_hi, w_lo, bias, res, y, x2, alpha2, beta2, part_da, part_db,
+                                          B, Cin, Cout, Tin, Tout, K, dil, pad, tanh_out, flags, stream);
+}
+// sat_conv1d_bf16x3_planesq that may split its launch: ws / ws_floats / split as sat_conv1d_bf16x3_ws (sat_conv_bf16x3_split(2, ...)).  A split launch
+// is one workgroup per (tile, split), whatever the persistence flags say.
+extern "C" int sat_conv1d_bf16x3_planesq_ws(const short* xp_hi, const short* xp_lo, int rows, const short* w_hi, const short* w_lo,
+                                            const float* bias, const float* res, float* y, const float* x2, const float* alpha2,
+                                            const float* beta2, float* part_da, float* part_db, int B, int Cin, int Cout, int Tin, int Tout,
+                                            int K, int dil, int pad, int tanh_out, int flags, float* ws, long long ws_floats, int split, void* stream) {
+    return sat_conv1d_bf16x3_planesq_impl("sat_conv1d_bf16x3_planesq_ws", xp_hi, xp_lo, rows, w_hi, w_lo, bias, res, y, x2, alpha2, beta2, part_da, part_db,
+                                          B, Cin, Cout, Tin, Tout, K, dil, pad, tanh_out, flags, stream, SatSplitWs{ws, ws_floats, split, 0});
 }
 
 // The whole ResidualUnit forward in one launch (autoencoders.py:58-83), C <= 128 channels:
@@ -787,11 +968,12 @@ extern "C" int sat_residual_unit_fwd(const short* xp_hi, const short* xp_lo, int
 
 // Same contract as sat_convtr1d (y[co][q*stride + k - pad] += W[ci][co][k] act(x)[ci][q], K == 2*stride, power-of-two
 // stride), weights as sat_pack_weights_bf16x3 planes (mode 2).
-extern "C" int sat_convtr1d_bf16x3(const float* x, const short* w_hi, const short* w_lo, const float* bias,
-                                   const float* snake_a, const float* snake_ib, const float* res, float* y,
-                                   const float* x2, const float* alpha2, const float* beta2, float* part_da,
-                                   float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride,
-                                   int pad, int tanh_out, void* stream) {
+static int sat_convtr1d_bf16x3_impl(const char* what, const float* x, const short* w_hi, const short* w_lo, const float* bias,
+                                    const float* snake_a, const float* snake_ib, const float* res, float* y,
+                                    const float* x2, const float* alpha2, const float* beta2, float* part_da,
+                                    float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride,
+                                    int pad, int tanh_out, void* stream, const SatSplitWs& sw = SAT_NO_SPLIT, SatConvBfLaunch* geom_only = nullptr,
+                                    SatBfPlan* plan_out = nullptr) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || Tin <= 0 || Tout <= 0) { sat_set_error("sat_convtr1d_bf16x3: empty shape"); return 1; }
     SatBfPlan pl;
     if (!sat_bf_plan(K, stride, 2, &pl) || pad < 0) { sat_set_error("sat_convtr1d_bf16x3: needs K == 2*stride with a power-of-two stride"); return 1; }
@@ -810,7 +992,60 @@ extern "C" int sat_convtr1d_bf16x3(const float* x, const short* w_hi, const shor
     a.in_shift = 0;
     a.out_shift = pad;
     a.nq = sat_cdiv(Tout + pad, stride);
-    return sat_bf_launch("sat_convtr1d_bf16x3", a, pl, stream);
+    if (geom_only) { *geom_only = a; *plan_out = pl; return 0; }
+    return sat_bf_launch(what, a, pl, stream, sw);
+}
+extern "C" int sat_convtr1d_bf16x3(const float* x, const short* w_hi, const short* w_lo, const float* bias,
+                                   const float* snake_a, const float* snake_ib, const float* res, float* y,
+                                   const float* x2, const float* alpha2, const float* beta2, float* part_da,
+                                   float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride,
+                                   int pad, int tanh_out, void* stream) {
+    return sat_convtr1d_bf16x3_impl("sat_convtr1d_bf16x3", x, w_hi, w_lo, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
+                                    B, Cin, Cout, Tin, Tout, K, stride, pad, tanh_out, stream);
+}
+// sat_convtr1d_bf16x3 that may split its launch: ws / ws_floats / split as sat_conv1d_bf16x3_ws (sat_conv_bf16x3_split(1, ...))
+extern "C" int sat_convtr1d_bf16x3_ws(const float* x, const short* w_hi, const short* w_lo, const float* bias,
+                                      const float* snake_a, const float* snake_ib, const float* res, float* y,
+                                      const float* x2, const float* alpha2, const float* beta2, float* part_da,
+                                      float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride,
+                                      int pad, int tanh_out, float* ws, long long ws_floats, int split, void* stream) {
+    return sat_convtr1d_bf16x3_impl("sat_convtr1d_bf16x3_ws", x, w_hi, w_lo, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
+                                    B, Cin, Cout, Tin, Tout, K, stride, pad, tanh_out, stream, SatSplitWs{ws, ws_floats, split, 0});
+}
+// How many ways the launch of a conv splits, and the workspace that takes: kind 0 = sat_conv1d_bf16x3 (Tin = Tout * stride is assumed: the count
+// does not depend on Tin), 1 = sat_convtr1d_bf16x3, 2 = sat_conv1d_bf16x3_planesq (stride ignored).  split: -1 the rule (sat_conv_split_rule), 0 off,
+// n >= 2 forced; cus: the CU count the rule assumes (<= 0: this device's).  Returns the split count (1: a plain launch), -1 where the shape is not
+// served or a forced count is not possible; *ws_floats (may be NULL): floats of workspace the _ws entry point needs.  Host code only.
+extern "C" int sat_conv_bf16x3_split(int kind, int B, int Cin, int Cout, int Tout, int K, int stride, int dil, int pad, int split, int cus,
+                                     long long* ws_floats) {
+    SatConvBfLaunch a;
+    SatBfPlan pl{8, 1, K};
+    int st = 1;
+    const float* one = reinterpret_cast<const float*>(16);       // (stands for "given" where the argument checks ask; never dereferenced)
+    if (ws_floats) *ws_floats = 0;
+    if (kind == 0) {
+        const int Tin = (Tout - 1) * stride + dil * (K - 1) + 1 - 2 * pad;
+        st = sat_conv1d_bf16x3_impl("sat_conv_bf16x3_split", nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                    nullptr, nullptr, B, Cin, Cout, Tin > 0 ? Tin : 1, Tout, K, stride, dil, pad, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                                    SAT_NO_SPLIT, &a, &pl);
+    } else if (kind == 1) {
+        st = sat_convtr1d_bf16x3_impl("sat_conv_bf16x3_split", nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                      nullptr, nullptr, B, Cin, Cout, 1, Tout, K, stride, pad, 0, nullptr, SAT_NO_SPLIT, &a, &pl);
+    } else if (kind == 2) {
+        const int rows = sat_conv1d_k7_plane_rows(Tout, Tout, pad);
+        st = sat_conv1d_bf16x3_planesq_impl("sat_conv_bf16x3_split", reinterpret_cast<const short*>(one), reinterpret_cast<const short*>(one), rows, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, Cin, Cout, Tout, Tout, K, dil,
+                                            pad, 0, 0, nullptr, SAT_NO_SPLIT, &a);
+    } else {
+        sat_set_error("sat_conv_bf16x3_split: kind 0 | 1 | 2");
+    }
+    if (st != 0) return -1;
+    int cps;
+    long long need;
+    const int n = sat_bf_split_decide(a, pl, split, cus, &cps, &need);
+    if (n < 0) { sat_set_error("sat_conv_bf16x3_split: this launch cannot be split that many ways"); return -1; }
+    if (ws_floats) *ws_floats = need;
+    return n;
 }
 // rows of the snake-gradient partial-sum planes written by sat_conv1d_bf16x3 (one per batch item and time tile)
 extern "C" int sat_conv1d_bf16x3_partial_rows(int B, int Tout, int K, int stride) {

@@ -17,6 +17,11 @@
 //     is overwritten from the phase after the barrier that retired its last reads.
 //   * epilogue: conv_epilogue.h (bias, dsnake + its per-channel sums, residual, tanh, plane emission; 16-byte accesses through an LDS
 //     transposition that reuses the drained stage memory).
+//   * split over input-channel chunks (SatConvBfLaunch::nsplit, sat_conv_split_rule in conv1d_bf16x3.hip): a launch of a few tiles with a long K loop
+//     (2048 -> 64 channels on 1024 steps: four workgroups of 128 chunks) runs nsplit workgroups per tile through the one-tile-per-workgroup
+//     instantiation — each the schedule below over its own chunk range, the range's first chunk in the stage of its parity, nothing requested
+//     past the range's end — and stores its raw accumulators to a slab; the finish launch (empty range) starts from the slabs' sum in index
+//     order and runs the epilogue.  Persistence has nothing to prefetch across ranges of 8 chunks and is not combined with it.
 //   * round 6 (VARIANT 3, the shipped K loop): the next chunk's LDS-DMA is issued INSIDE the MFMA sections, not beside the fragment reads
 //     (the item above describes VARIANT 1, kept as the A / B arm: SatConvBfLaunch::dma_in_mfma, ops.k7q_dma_in_mfma) — see INMFMA below.
 #pragma once
@@ -129,6 +134,22 @@ __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatCon
     const int co_tiles = a.cout_pad / CO_T, t_tiles = (a.nq + T_T - 1) / T_T;
     const int total_tiles = co_tiles * t_tiles * p.B;
     int tile_id = (int)blockIdx.x;
+    // split over input-channel chunks (SatConvBfLaunch::nsplit; the one-tile-per-workgroup instantiations only): workgroup (tile, z_s) — split z_s
+    // of every tile, then split z_s + 1 of every tile — runs chunks [c_lo, c_hi) with the schedule below and stores its raw accumulators; the
+    // finish launch (cps == 0) has an empty range and starts from the slabs' sum
+    constexpr bool CAN_SPLIT = !FUSED && !PERSIST;
+    bool split_on = false, split_fin = false;
+    int z_s = 0, c_lo = 0, c_hi = nchunks;
+    if constexpr (CAN_SPLIT) {
+        split_on = a.nsplit > 1;                          // block-uniform (kernel argument)
+        split_fin = split_on && a.cps == 0;
+        if (split_on) {
+            z_s = tile_id / total_tiles;
+            tile_id -= z_s * total_tiles;
+            c_lo = z_s * a.cps;
+            c_hi = c_lo + a.cps < nchunks ? c_lo + a.cps : nchunks;
+        }
+    }
     int co_tile, win;
     sat_xcd_tile(tile_id, co_tiles, t_tiles * p.B, &co_tile, &win);
     int b = win / t_tiles, t_tile = win - b * t_tiles;
@@ -217,6 +238,9 @@ __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatCon
     };
 
     bool wave_on_co = (co0 + co_w) < a.cout_v;            // Cout <= 64 (one co half empty): that wave row multiplies nothing
+    if constexpr (CAN_SPLIT) {
+        if (split_fin && wave_on_co) sat_split_sum<NT / 64>(a.ws, tile_id, a.nsplit, wave, lane, acc, true);
+    }
 #if !defined(SAT_HIPEMU)
     // De-phase the CUs: the first wave of workgroups starts everywhere at once and every tile takes the same time, so all 256 CUs
     // would reach their epilogues — 128 KiB of stores (+ two loads of the same size in a data-gradient) each — in the same few
@@ -227,21 +251,22 @@ __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatCon
         for (int i = 0; i < steps; ++i) __builtin_amdgcn_s_sleep(127);
     }
 #endif
-    // prologue: chunk 0 complete in its stage
+    // prologue: the range's first chunk complete in its stage (nothing for an empty range: no chunk at or past c_hi is ever requested)
     auto issue_chunk0 = [&]() {
+        const int st0 = (c_lo + SPAR) & 1;
 #pragma unroll
-        for (int tap = 0; tap < SAT_K7Q_TAPS; ++tap) issue_w(0, SPAR, tap);
-        issue_a(0, SPAR, 0); issue_a(0, SPAR, 1); issue_a(0, SPAR, 2);
+        for (int tap = 0; tap < SAT_K7Q_TAPS; ++tap) issue_w(c_lo, st0, tap);
+        issue_a(c_lo, st0, 0); issue_a(c_lo, st0, 1); issue_a(c_lo, st0, 2);
     };
-    issue_chunk0();
+    if (c_lo < c_hi) issue_chunk0();
   for (;;) {                                               // (one pass unless PERSIST)
     SAT_WAIT_VMCNT(0);
     SAT_RAW_BARRIER();
     if (wr == 1) SAT_RAW_BARRIER();                        // the second wave row runs one barrier behind the first
 
-    for (int c = 0; c < nchunks; ++c) {
+    for (int c = c_lo; c < c_hi; ++c) {
         const char* sb = lds + ((c + SPAR) & 1) * SAT_K7Q_STAGE;
-        const bool more = c + 1 < nchunks;
+        const bool more = c + 1 < c_hi;
         // ---- phase 0: taps 0..3 ----
 #pragma unroll
         for (int u = 0; u < 4; ++u) load_frags(fr[u], sb, u);
@@ -317,6 +342,12 @@ __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatCon
     }
     if (wr == 0) SAT_RAW_BARRIER();                        // pairs with the second wave row's last barrier
     __syncthreads();                                       // every wave is done with the stages: their memory serves the epilogue
+    if constexpr (CAN_SPLIT) {
+        if (split_on && !split_fin) {                      // split launch: the raw accumulators to this split's slab, no epilogue
+            if (wave_on_co) sat_split_store<NT / 64>(a.ws, tile_id, z_s, a.nsplit, wave, lane, acc, true);
+            return;
+        }
+    }
     // this tile's coordinates for the epilogue; PERSIST: the next tile's become current for the DMA lambdas
     const int e_b = b, e_t_tile = t_tile, e_co0 = co0, e_t0 = t0;
     bool have_next = false;
@@ -449,10 +480,18 @@ __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatCon
   }
 }
 
-static void sat_bf_launch_k7q(SatConvBfLaunch& a, void* stream) {
+// zmul: workgroups per tile (the split launch of sat_bf_launch: SatConvBfLaunch::nsplit; 1 otherwise)
+static void sat_bf_launch_k7q(SatConvBfLaunch& a, void* stream, unsigned zmul = 1) {
     const long long total = (long long)(a.cout_pad / SAT_K7_CO) * sat_cdiv(a.nq, SAT_K7_T) * a.p.B;
     a.stagger = 1;                                         // measured: -1 % forward, -2.5 % data-gradient (tools/kq_ab.py); 2 and 4 lose
     if (total < 1024) a.stagger = 0;                       // few tiles per CU: the delay would not be paid back
+    if (a.nsplit > 1) {
+        // split and finish launches: one tile (and split) per workgroup — persistence has nothing to prefetch across ranges of a few chunks
+        a.stagger = 0;
+        if (a.dma_in_mfma) { SAT_LAUNCH((sat_conv1d_bf16x3_k7q_kernel<3>), dim3((unsigned)total * zmul), dim3(SAT_K7_NT), stream, a); }
+        else { SAT_LAUNCH((sat_conv1d_bf16x3_k7q_kernel<1>), dim3((unsigned)total * zmul), dim3(SAT_K7_NT), stream, a); }
+        return;
+    }
     if (a.ru_w1_hi) { SAT_LAUNCH((sat_conv1d_bf16x3_k7q_kernel<1, true>), dim3((unsigned)total), dim3(SAT_K7_NT), stream, a); return; }
     const int cus = sat_cu_count();
     if (a.persist == 2 && total >= 2) {                    // test hook (flags bit 1): persistent at ANY size, three tiles per workgroup

@@ -108,6 +108,7 @@ class SatOps:
         self._zpage = None          # _zeros_page
         self._disc_pool, self._disc_gen, self._disc_geoms = {}, {}, {}      # _disc_plane_buf / disc_geom
         self._disc_emitted = None   # disc_register
+        self._split_plans = {}      # _conv_split_ws: (shape, knob, device) -> (split count, workspace floats), what the library answered
 
     # ------------------------------------------------------------------ plumbing
     def _stream(self, t):
@@ -359,8 +360,34 @@ class SatOps:
         self._f32(out)
         return out
 
+    # split over input-channel chunks (csrc/conv1d_bf16x3.hip, sat_conv_split_rule): conv launches of few tiles and a long K loop — the bottom of
+    # the U — run n workgroups per tile + a finish launch of the same kernel.  None: the rule decides (CUs x resident workgroups / tiles, at
+    # least 8 chunks per split); 0: never (A/B: bench.py --ops-set conv_split=0); n >= 2: n splits wherever the launch can have them (the tests'
+    # small shapes), a plain launch elsewhere.
+    conv_split = None
+
+    def _conv_split_ws(self, kind, x, cout, tout, k, stride, dil, pad):
+        """-> (slabs, split): the workspace and the `split` argument of a _ws entry point (kind as sat_conv_bf16x3_split), or (None, 0) for a
+        plain launch.  The slabs come from the workspace cache, one per shape and stream: a captured graph keeps their address."""
+        want = -1 if self.conv_split is None else int(self.conv_split)
+        if want == 0:
+            return None, 0
+        b, cin, _ = x.shape
+        shape = (kind, b, cin, cout, tout, k, stride, dil, pad)
+        plan = self._split_plans.get((shape, want, x.device))
+        if plan is None:
+            need = ctypes.c_longlong(0)
+            n = self.lib.sat_conv_bf16x3_split(*shape, want, 0, ctypes.byref(need))
+            plan = self._split_plans[(shape, want, x.device)] = (n, need.value)
+        n, need = plan
+        if n < 2:
+            return None, 0
+        st = self._stream(x)
+        return self._workspace(("conv_split", shape, n, x.device, st.value if st is not None else 0), need, torch.float32, x.device), n
+
     def _bf16x3_call(self, fn, rows, x, w_planes, cout, tout, dims, bias, snake, res, tanh_out, dsnake, out=None, sconsts=None, emit=None):
         b, cin, tin = x.shape
+        transposed = len(dims) == 3                     # (k, stride, pad): sat_convtr1d_bf16x3; (k, stride, dil, pad): sat_conv1d_bf16x3
         self._f32(x, bias, res)
         sa = sib = None
         if snake is not None:
@@ -371,7 +398,13 @@ class SatOps:
         args = (_ptr(x), _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(sa), _ptr(sib),
                 _ptr(res), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb),
                 b, cin, cout, tin, tout, *dims, int(tanh_out))
-        if emit:
+        slabs, split = self._conv_split_ws(1 if transposed else 0, x, cout, tout, dims[0], dims[1], 1 if transposed else dims[2], dims[-1])
+        if slabs is not None and transposed:
+            self._chk(self.lib.sat_convtr1d_bf16x3_ws(*args, _ptr(slabs), slabs.numel(), split, self._stream(x)))
+        elif slabs is not None:
+            self._chk(self.lib.sat_conv1d_bf16x3_ws(*args, _ptr(ep.hi), _ptr(ep.lo), _ptr(ea), _ptr(eib), ep.rows, _ptr(slabs), slabs.numel(), split,
+                                                    self._stream(x)))
+        elif emit:
             # plane emission (sat_conv1d_bf16x3_emit): the planes the k7 conv that consumes y next would otherwise build in a pre-pass
             self._chk(self.lib.sat_conv1d_bf16x3_emit(*args, _ptr(ep.hi), _ptr(ep.lo), _ptr(ea), _ptr(eib), ep.rows, self._stream(x)))
         else:
@@ -592,9 +625,14 @@ class SatOps:
         kept = xp if own is not None and xp.own is own and k == 7 and cout == cin else None
         y = self._conv_out(out, b, cout, tout, x.device)
         x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, prows, x.device)
-        self._chk(self.lib.sat_conv1d_bf16x3_planesq(_ptr(xp.hi), _ptr(xp.lo), xp.rows, _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(res),
-                                                     _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb), b, cin, cout, tin, tout,
-                                                     k, dil, pad, int(tanh_out), {True: 0, False: 1, "force": 2}[self.k7q_persist] | (4 if self.k7q_dma_in_mfma else 0), st))
+        args = (_ptr(xp.hi), _ptr(xp.lo), xp.rows, _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(res),
+                _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb), b, cin, cout, tin, tout,
+                k, dil, pad, int(tanh_out), {True: 0, False: 1, "force": 2}[self.k7q_persist] | (4 if self.k7q_dma_in_mfma else 0))
+        slabs, split = self._conv_split_ws(2, x, cout, tout, k, 1, dil, pad)
+        if slabs is not None:
+            self._chk(self.lib.sat_conv1d_bf16x3_planesq_ws(*args, _ptr(slabs), slabs.numel(), split, st))
+        else:
+            self._chk(self.lib.sat_conv1d_bf16x3_planesq(*args, st))
         y = self._dsnake_result(y, pda, pdb)
         return (y, kept) if keep_planes else y
 
