@@ -698,161 +698,8 @@ extern "C" int sat_conv_split_rule(int tiles, int nchunks, int resident, int cus
     const int cps = sat_cdiv(nchunks, (int)n);
     return sat_cdiv(nchunks, cps);
 }
-// what the rule looks at, for one launch: (0 tiles: a kernel that does not split — the direct k7 kernel, the fused unit)
-struct SatSplitGeom { int tiles, nchunks, resident, slab; };
-static SatSplitGeom sat_bf_split_geom(const SatConvBfLaunch& a, const SatBfPlan& pl) {
-    if (pl.ng == 8 && pl.cs == 1 && a.sin_log2 == 0 && a.sout_log2 == 0) {
-        if (!(a.xp_hi && a.wq) || a.ru_w1_hi) return SatSplitGeom{0, 0, 0, 0};
-        return SatSplitGeom{(a.cout_pad / SAT_K7_CO) * sat_cdiv(a.nq, SAT_K7_T) * a.p.B, sat_cdiv(a.cin_v, 16), 1, SAT_SPLIT_SLAB(SAT_K7_NT / 64)};
-    }
-    return SatSplitGeom{sat_cdiv(a.nq, SAT_T_T) * (a.cout_pad / SAT_CO_T) * a.p.B, sat_cdiv(a.cin_v, 8 * pl.cs), pl.ng == 4 ? 3 : 2, SAT_SPLIT_SLAB(4)};
-}
-// want: < 0 the rule, 0 no split, n >= 2 exactly n splits.  Returns the split count (1: none), or -1 for a forced count the launch cannot have
-// (a kernel that does not split, more splits than chunks, or a count that would leave a split without chunks).  *ws_floats: the slabs' size.
-static int sat_bf_split_decide(const SatConvBfLaunch& a, const SatBfPlan& pl, int want, int cus, int* cps, long long* ws_floats) {
-    const SatSplitGeom g = sat_bf_split_geom(a, pl);
-    int n = 1;
-    *cps = 0;
-    *ws_floats = 0;
-    if (want == 0 || want == 1) return 1;
-    if (want < 0) {
-        if (g.tiles == 0) return 1;
-        n = sat_conv_split_rule(g.tiles, g.nchunks, g.resident, cus > 0 ? cus : sat_cu_count());
-        if (n < 2) return 1;
-    } else {
-        if (g.tiles == 0 || want > SAT_SPLIT_MAX || want > g.nchunks) return -1;
-        if (sat_cdiv(g.nchunks, sat_cdiv(g.nchunks, want)) != want) return -1;
-        n = want;
-    }
-    *cps = sat_cdiv(g.nchunks, n);
-    *ws_floats = (long long)g.tiles * n * g.slab;
-    return n;
-}
-// the split state of one call through a _ws entry point (the plain entry points: no workspace, no split)
-struct SatSplitWs { float* ws; long long ws_floats; int want; int cus; };
-static const SatSplitWs SAT_NO_SPLIT{nullptr, 0, 0, 0};
 
-static int sat_bf_launch_one(const char* what, SatConvBfLaunch& a, const SatBfPlan& pl, void* stream);
-static int sat_bf_launch(const char* what, SatConvBfLaunch& a, const SatBfPlan& pl, void* stream, const SatSplitWs& sw = SAT_NO_SPLIT) {
-    int cps;
-    long long need;
-    const int n = sat_bf_split_decide(a, pl, sw.want, sw.cus, &cps, &need);
-    if (n < 0) { sat_set_error("conv1d_bf16x3: this launch cannot be split that many ways (2 <= n <= chunks, every split at least one chunk; the direct k7 kernel and the fused unit do not split)"); return 1; }
-    if (n < 2) return sat_bf_launch_one(what, a, pl, stream);
-    if (!sw.ws || sw.ws_floats < need || ((uintptr_t)sw.ws & 15)) { sat_set_error("conv1d_bf16x3: the split workspace is missing, misaligned or smaller than sat_conv_bf16x3_split asks for"); return 1; }
-    a.ws = sw.ws;
-    a.nsplit = n;
-    a.cps = cps;                                           // split launch: n workgroups per tile
-    if (const int st = sat_bf_launch_one(what, a, pl, stream)) return st;
-    a.cps = 0;                                             // finish launch: the slabs' sum and the epilogue
-    return sat_bf_launch_one(what, a, pl, stream);
-}
-
-static int sat_bf_launch_one(const char* what, SatConvBfLaunch& a, const SatBfPlan& pl, void* stream) {
-    const unsigned zmul = (a.nsplit > 1 && a.cps > 0) ? (unsigned)a.nsplit : 1u;      // workgroups per tile
-    if (pl.ng == 8 && pl.cs == 1 && a.sin_log2 == 0 && a.sout_log2 == 0) {
-        if (a.xp_hi && a.wq) sat_bf_launch_k7q(a, stream, zmul);
-        else sat_bf_launch_k7(a, stream);
-        return sat_check_launch(what);
-    }
-    // the generic kernel stages the input's SnakeBeta constants of ALL channels in LDS: 1024 channels on the k = 1 plan (4, 4), 2048 on the others
-    // (every Oobleck level: channels 128 x c_mults <= 16)
-    if (a.p.alpha && a.p.Cin > ((pl.ng == 4) ? 1024 : 2048)) {
-        sat_set_error("conv1d_bf16x3: an activated input of more than 2048 channels (1024 for K <= 4 at stride 1) is not served by the bf16x3 kernels (ops.use_bf16x3 = False takes the fp32-MFMA ones)");
-        return 1;
-    }
-    dim3 grid(sat_cdiv(a.nq, SAT_T_T), a.cout_pad / SAT_CO_T, a.p.B * zmul);
-    if (a.sin_log2 > 0) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 4, true>), grid, dim3(256), stream, a); }     // strided: always plan (8, 4)
-    else if (pl.ng == 8 && pl.cs == 1) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 1, false>), grid, dim3(256), stream, a); }
-    else if (pl.ng == 8 && pl.cs == 2) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 2, false>), grid, dim3(256), stream, a); }
-    else if (pl.ng == 8 && pl.cs == 4) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 4, false>), grid, dim3(256), stream, a); }
-    else { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<4, 4, false>), grid, dim3(256), stream, a); }
-    return sat_check_launch(what);
-}
-
-// Same contract as sat_conv1d (y[co][t] = sum W[co][ci][k] act(x)[ci][t*stride + k*dil - pad]), with the weights given
-// as sat_pack_weights_bf16x3 planes (mode 0, or mode 1 for a stride-1 data-gradient) and the SnakeBeta constants given
-// pre-exponentiated (sat_snake_consts), or NULL for no activation.  stride 1: K <= 8; stride S: K == 2S, S a power of two.
-static int sat_conv1d_bf16x3_impl(const char* what, const float* x, const short* w_hi, const short* w_lo, const float* bias,
-                                  const float* snake_a, const float* snake_ib, const float* res, float* y,
-                                  const float* x2, const float* alpha2, const float* beta2, float* part_da,
-                                  float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil,
-                                  int pad, int tanh_out, short* em_hi, short* em_lo, const float* em_a, const float* em_ib, int em_rows,
-                                  void* stream, const SatSplitWs& sw = SAT_NO_SPLIT, SatConvBfLaunch* geom_only = nullptr, SatBfPlan* plan_out = nullptr) {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || Tin <= 0 || Tout <= 0) { sat_set_error("sat_conv1d_bf16x3: empty shape"); return 1; }
-    SatBfPlan pl;
-    if (!sat_bf_plan(K, stride, 0, &pl) || dil < 1 || (stride > 1 && dil != 1)) {
-        sat_set_error("sat_conv1d_bf16x3: needs stride 1 with K <= 8, or K == 2*stride (power-of-two stride, dilation 1)");
-        return 1;
-    }
-    if ((pl.kv - 1) * dil > (pl.cs == 1 ? 62 : SAT_BF_AROWSN - SAT_T_T)) { sat_set_error("sat_conv1d_bf16x3: receptive field too large for the LDS slab"); return 1; }
-    if ((snake_a == nullptr) != (snake_ib == nullptr)) { sat_set_error("sat_conv1d_bf16x3: snake constants must both be given"); return 1; }
-    if (x2 && (!alpha2 || !beta2 || !part_da || !part_db)) { sat_set_error("sat_conv1d_bf16x3: backward epilogue needs alpha2/beta2/partials"); return 1; }
-    SatConvBfLaunch a;
-    a.p = SatConvParams{x, nullptr, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
-                        B, Cin, Cout, Tin, Tout, pl.kv, 1, dil, stride == 1 ? pad : 0, tanh_out};
-    a.w_hi = w_hi;
-    a.w_lo = w_lo;
-    a.cout_v = Cout;
-    a.cout_pad = sat_cdiv(Cout, SAT_CO_T) * SAT_CO_T;
-    a.cin_v = Cin * stride;
-    a.sin_log2 = sat_log2i(stride);
-    a.sout_log2 = 0;
-    a.in_shift = stride == 1 ? 0 : pad;
-    a.out_shift = 0;
-    a.nq = Tout;
-    if (em_hi) {
-        // plane emission lives in the generic kernel's 16-byte epilogue
-        const bool generic = !(pl.ng == 8 && pl.cs == 1);
-        const bool vec4 = (Tout & 3) == 0 && (((uintptr_t)y | (uintptr_t)x2 | (uintptr_t)res) & 15) == 0;
-        if (!generic || !vec4 || !em_lo || (em_a == nullptr) != (em_ib == nullptr) || em_rows < SAT_K7P_LEAD_ROWS + Tout ||
-            (((uintptr_t)em_hi | (uintptr_t)em_lo) & 15)) {
-            sat_set_error("sat_conv1d_bf16x3_emit: emission needs K <= 4 or a strided conv, Tout % 4 == 0, 16-byte aligned tensors, rows >= 32 + Tout");
-            return 1;
-        }
-        a.em_hi = em_hi; a.em_lo = em_lo; a.em_a = em_a; a.em_ib = em_ib; a.em_rows = em_rows; a.em_c8 = sat_cdiv(Cout, 8);
-    }
-    if (geom_only) { *geom_only = a; *plan_out = pl; return 0; }     // (sat_conv_bf16x3_split: the launch's geometry, nothing enqueued)
-    return sat_bf_launch(what, a, pl, stream, sw);
-}
-extern "C" int sat_conv1d_bf16x3(const float* x, const short* w_hi, const short* w_lo, const float* bias,
-                                 const float* snake_a, const float* snake_ib, const float* res, float* y,
-                                 const float* x2, const float* alpha2, const float* beta2, float* part_da,
-                                 float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil,
-                                 int pad, int tanh_out, void* stream) {
-    return sat_conv1d_bf16x3_impl("sat_conv1d_bf16x3", x, w_hi, w_lo, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
-                                  B, Cin, Cout, Tin, Tout, K, stride, dil, pad, tanh_out, nullptr, nullptr, nullptr, nullptr, 0, stream);
-}
-// sat_conv1d_bf16x3 that ALSO writes act(y) as the activation planes of the k7 conv that consumes y next (sat_conv1d_bf16x3_planes /
-// _planesq): em_hi / em_lo [B][ceil(Cout/8)][em_rows][8] bf16 (row 32 + t; the caller keeps the rows around the sequence zero),
-// em_a / em_ib the consumer's pre-exponentiated SnakeBeta constants (sat_snake_consts) or NULL for planes of y itself.  The k = 1 /
-// K <= 4 / strided plans only (the producers of a ResidualUnit's input), Tout % 4 == 0.
-extern "C" int sat_conv1d_bf16x3_emit(const float* x, const short* w_hi, const short* w_lo, const float* bias,
-                                      const float* snake_a, const float* snake_ib, const float* res, float* y,
-                                      const float* x2, const float* alpha2, const float* beta2, float* part_da,
-                                      float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil,
-                                      int pad, int tanh_out, void* em_hi, void* em_lo, const float* em_a, const float* em_ib, int em_rows,
-                                      void* stream) {
-    if (!em_hi) { sat_set_error("sat_conv1d_bf16x3_emit: planes missing"); return 1; }
-    return sat_conv1d_bf16x3_impl("sat_conv1d_bf16x3_emit", x, w_hi, w_lo, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
-                                  B, Cin, Cout, Tin, Tout, K, stride, dil, pad, tanh_out, (short*)em_hi, (short*)em_lo, em_a, em_ib, em_rows, stream);
-}
-
-// sat_conv1d_bf16x3 / _emit (em_hi NULL: no emission) that may SPLIT its launch over input-channel chunks (sat_conv_split_rule): ws = a workspace of
-// ws_floats floats, at least what sat_conv_bf16x3_split(0, ...) reports for the same `split` (-1: the rule, 0: off, n >= 2: exactly n — status 1
-// and no launch where the launch cannot be split that way).  The workspace is written by the first launch and read by the second.
-extern "C" int sat_conv1d_bf16x3_ws(const float* x, const short* w_hi, const short* w_lo, const float* bias,
-                                    const float* snake_a, const float* snake_ib, const float* res, float* y,
-                                    const float* x2, const float* alpha2, const float* beta2, float* part_da,
-                                    float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil,
-                                    int pad, int tanh_out, void* em_hi, void* em_lo, const float* em_a, const float* em_ib, int em_rows,
-                                    float* ws, long long ws_floats, int split, void* stream) {
-    return sat_conv1d_bf16x3_impl("sat_conv1d_bf16x3_ws", x, w_hi, w_lo, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
-                                  B, Cin, Cout, Tin, Tout, K, stride, dil, pad, tanh_out, (short*)em_hi, (short*)em_lo, em_a, em_ib, em_rows, stream,
-                                  SatSplitWs{ws, ws_floats, split, 0});
-}
-
-// ---- the k = 5..7 stride-1 convs from pre-split activation planes (conv1d_planes.h, conv1d_bf16x3_k7q.h) ----
+// ---- activation planes of the k = 5..7 stride-1 convs (conv1d_planes.h, conv1d_bf16x3_k7q.h) ----
 // rows of one (batch, 8-channel chunk) plane: 32 zero rows, the sequence, zero rows up to the last window's halo
 extern "C" int sat_conv1d_k7_plane_rows(int Tin, int Tout, int pad) {
     if (Tin <= 0 || Tout <= 0 || pad < 0 || pad > SAT_K7P_LEAD) return -1;
@@ -869,51 +716,254 @@ extern "C" int sat_conv1d_k7_planes(const float* x, const float* snake_a, const 
     SAT_LAUNCH(sat_k7_planes_kernel, dim3(sat_cdiv(rows, 256), p.c8, B), dim3(256), stream, p);
     return sat_check_launch("sat_conv1d_k7_planes");
 }
+
+// ------------------------------------------------------------------------------------------------
+// One launch = a SHAPE (integers), the KERNEL that serves it and its OPERANDS (pointers).  Every launching entry point fills a shape and an
+// operand record and calls sat_bf_run: sat_bf_geometry (every shape check; the virtual stride-1 conv of "Plans" above) -> sat_bf_kernel ->
+// sat_bf_bind (every pointer check) -> sat_bf_split_decide -> the launch, or the split and the finish launch.  The host-only queries
+// (sat_conv_bf16x3_split, *_partial_rows) stop after sat_bf_kernel.
+// ------------------------------------------------------------------------------------------------
+enum SatBfKind { SAT_BF_CONV = 0, SAT_BF_CONVTR = 1, SAT_BF_PLANES = 2, SAT_BF_UNIT = 3 };      // 0 .. 2: the `kind` of sat_conv_bf16x3_split
+struct SatBfShape {
+    int kind, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, tanh_out;
+    int rows;              // SAT_BF_PLANES / _UNIT: rows of an input plane
+    int flags;             // SAT_BF_PLANES: bit 0: one workgroup per tile (round 5's launch; A/B runs and the tests' second arm); bit 1: persistent at
+                           // any size (the tests: small shapes); bit 2: VARIANT 3 of the k7q kernel
+};
+struct SatBfInput { const float* x; const float* snake_a; const float* snake_ib; };     // fp32 input, its pre-exponentiated SnakeBeta constants or null
+struct SatBfPlanesIn { const short* hi; const short* lo; };                             // SAT_BF_PLANES / _UNIT: the (activated) input as planes
+struct SatBfOutput { const float* bias; const float* res; float* y; };
+struct SatBfDgrad { const float* x2; const float* alpha2; const float* beta2; float* part_da; float* part_db; };      // data-gradient epilogue: all five or none
+struct SatBfEmit { short* hi; short* lo; const float* a; const float* ib; int rows; };  // plane emission (hi null: none)
+struct SatBfUnit { const short* w1_hi; const short* w1_lo; const float* bias2; const float* a2; const float* ib2; float* h; };   // fused unit: its second conv
+struct SatBfOperands {
+    SatBfInput in;
+    SatBfPlanesIn xp;
+    const short* w_hi;
+    const short* w_lo;
+    SatBfOutput out;
+    SatBfDgrad dg;
+    SatBfEmit em;
+    SatBfUnit ru;
+};
+
+// WHICH KERNEL SERVES A LAUNCH — asked here and nowhere else — and what the host needs to know of that kernel.
+enum SatBfKernelId { SAT_BF_K7, SAT_BF_K7Q, SAT_BF_K7Q_FUSED, SAT_BF_GENERIC };       // direct k7, planes k7q, the fused unit, sat_conv1d_bf16x3_kernel
+struct SatBfKernel {
+    SatBfKernelId id;
+    int ng, cs;            // SAT_BF_GENERIC: the instantiation <ng, cs, strided>
+    bool strided;
+    int co_t, t_t;         // output tile: channels x time steps
+    int chunk;             // input channels per step of the K loop
+    int resident;          // workgroups per CU
+    int slab;              // floats of a workgroup's accumulators in the split workspace; 0: the kernel does not split
+    bool emits;            // its epilogue can write the consumer's planes
+};
+static SatBfKernel sat_bf_kernel(int kind, const SatBfPlan& pl, const SatConvBfLaunch& a) {
+    if (pl.ng == 8 && pl.cs == 1 && a.sin_log2 == 0 && a.sout_log2 == 0) {       // 5 <= K <= 8 at stride 1: the 128 x 256 tile, 512 threads
+        const SatBfKernelId id = kind == SAT_BF_UNIT ? SAT_BF_K7Q_FUSED : kind == SAT_BF_PLANES ? SAT_BF_K7Q : SAT_BF_K7;
+        return SatBfKernel{id, 8, 1, false, SAT_K7_CO, SAT_K7_T, id == SAT_BF_K7 ? 8 : 16, 1, id == SAT_BF_K7Q ? SAT_SPLIT_SLAB(SAT_K7_NT / 64) : 0,
+                           id == SAT_BF_K7Q_FUSED};
+    }
+    return SatBfKernel{SAT_BF_GENERIC, pl.ng, pl.cs, a.sin_log2 > 0, SAT_CO_T, SAT_T_T, 8 * pl.cs, pl.ng == 4 ? 3 : 2, SAT_SPLIT_SLAB(4), true};
+}
+
+static int sat_bf_fail(const char* who, const char* msg) {
+    char buf[512];
+    snprintf(buf, sizeof(buf), "%s: %s", who, msg);
+    sat_set_error(buf);
+    return 1;
+}
+
+// shape -> plan + launch with every non-pointer field set; 1 and sat_last_error() where the family does not serve the shape
+static int sat_bf_geometry(const char* who, const SatBfShape& s, SatBfPlan* pl, SatConvBfLaunch* out) {
+    const bool unit = s.kind == SAT_BF_UNIT;
+    if (s.B <= 0 || s.Cin <= 0 || s.Cout <= 0 || s.Tin <= 0 || s.Tout <= 0) return sat_bf_fail(who, unit ? "needs 1 <= C <= 128" : "empty shape");
+    SatConvBfLaunch a{};
+    a.cin_v = s.Cin;
+    a.cout_v = s.Cout;
+    a.nq = s.Tout;
+    int vdil = s.dil, vpad = s.pad;                           // of the virtual stride-1 conv
+    if (s.kind == SAT_BF_CONV) {
+        if (!sat_bf_plan(s.K, s.stride, 0, pl) || s.dil < 1 || (s.stride > 1 && s.dil != 1))
+            return sat_bf_fail(who, "needs stride 1 with K <= 8, or K == 2*stride (power-of-two stride, dilation 1)");
+        if ((pl->kv - 1) * s.dil > (pl->cs == 1 ? 62 : SAT_BF_AROWSN - SAT_T_T)) return sat_bf_fail(who, "receptive field too large for the LDS slab");
+        a.cin_v = s.Cin * s.stride;
+        a.sin_log2 = sat_log2i(s.stride);
+        if (s.stride > 1) { a.in_shift = s.pad; vpad = 0; }
+    } else if (s.kind == SAT_BF_CONVTR) {
+        if (!sat_bf_plan(s.K, s.stride, 2, pl) || s.pad < 0) return sat_bf_fail(who, "needs K == 2*stride with a power-of-two stride");
+        a.cout_v = s.Cout * s.stride;
+        a.sout_log2 = sat_log2i(s.stride);
+        a.out_shift = s.pad;
+        a.nq = sat_cdiv(s.Tout + s.pad, s.stride);
+        vdil = vpad = 1;
+    } else {
+        if (unit && s.Cout > SAT_K7_CO) return sat_bf_fail(who, "needs 1 <= C <= 128");
+        if (s.K < 5 || s.K > SAT_K7Q_TAPS || s.dil < 1 || (s.K - 1) * s.dil > 62 || (unit && 2 * s.pad != (s.K - 1) * s.dil))
+            return sat_bf_fail(who, unit ? "needs 5 <= K <= 7, (K-1)*dil <= 62, 'same' padding" : "needs stride 1, 5 <= K <= 7, (K-1)*dil <= 62");
+        if (s.rows < sat_conv1d_k7_plane_rows(s.Tin, s.Tout, s.pad))
+            return sat_bf_fail(who, unit ? "rows must be >= sat_conv1d_k7_plane_rows(T, T, pad)" : "rows must be >= sat_conv1d_k7_plane_rows(Tin, Tout, pad)");
+        *pl = SatBfPlan{8, 1, s.K};
+        a.xp_rows = s.rows;
+        a.xp_c8 = sat_cdiv(s.Cin, 8);
+        a.wq = 1;
+        if (!unit) {
+            a.dma_in_mfma = (s.flags & 4) ? 1 : 0;
+            a.persist = (s.flags & 1) ? 0 : ((s.flags & 2) ? 2 : 1);
+        }
+    }
+    a.cout_pad = sat_cdiv(a.cout_v, SAT_CO_T) * SAT_CO_T;
+    a.p.B = s.B; a.p.Cin = s.Cin; a.p.Cout = s.Cout; a.p.Tin = s.Tin; a.p.Tout = s.Tout;
+    a.p.K = pl->kv; a.p.stride = 1; a.p.dil = vdil; a.p.pad = vpad; a.p.tanh_out = s.tanh_out;
+    *out = a;
+    return 0;
+}
+
+// the pointer-dependent checks, once, then the pointers into the launch
+static int sat_bf_bind(const char* who, const SatBfKernel& k, const SatBfOperands& o, SatConvBfLaunch* a) {
+    const bool fused = k.id == SAT_BF_K7Q_FUSED;
+    if ((o.in.snake_a == nullptr) != (o.in.snake_ib == nullptr)) return sat_bf_fail(who, "snake constants must both be given");
+    if (o.dg.x2 && (!o.dg.alpha2 || !o.dg.beta2 || !o.dg.part_da || !o.dg.part_db)) return sat_bf_fail(who, "backward epilogue needs alpha2/beta2/partials");
+    if (k.id == SAT_BF_K7Q && (!o.xp.hi || !o.xp.lo)) return sat_bf_fail(who, "activation planes missing");
+    if (fused && (!o.xp.hi || !o.xp.lo || !o.w_hi || !o.w_lo || !o.ru.w1_hi || !o.ru.w1_lo || !o.ru.a2 || !o.ru.ib2 || !o.out.res || !o.out.y))
+        return sat_bf_fail(who, "missing operand");
+    const bool vec4 = (a->p.Tout & 3) == 0 && (((uintptr_t)o.out.y | (uintptr_t)o.dg.x2 | (uintptr_t)o.out.res) & 15) == 0;       // the 16-byte epilogue
+    if (fused && !vec4) return sat_bf_fail(who, "T % 4 == 0 and 16-byte aligned x / y");
+    if (o.em.hi) {
+        if (!k.emits || !vec4 || !o.em.lo || (o.em.a == nullptr) != (o.em.ib == nullptr) || o.em.rows < SAT_K7P_LEAD_ROWS + a->p.Tout ||
+            (((uintptr_t)o.em.hi | (uintptr_t)o.em.lo) & 15))
+            return sat_bf_fail(who, fused ? "bad emission planes"
+                                          : "emission needs K <= 4 or a strided conv, Tout % 4 == 0, 16-byte aligned tensors, rows >= 32 + Tout");
+        a->em_hi = o.em.hi; a->em_lo = o.em.lo; a->em_a = o.em.a; a->em_ib = o.em.ib; a->em_rows = o.em.rows; a->em_c8 = sat_cdiv(a->p.Cout, 8);
+    }
+    a->p.x = o.in.x; a->p.alpha = o.in.snake_a; a->p.beta = o.in.snake_ib;
+    a->xp_hi = o.xp.hi; a->xp_lo = o.xp.lo;
+    a->w_hi = o.w_hi; a->w_lo = o.w_lo;
+    a->p.bias = o.out.bias; a->p.res = o.out.res; a->p.y = o.out.y;
+    a->p.x2 = o.dg.x2; a->p.alpha2 = o.dg.alpha2; a->p.beta2 = o.dg.beta2; a->p.part_da = o.dg.part_da; a->p.part_db = o.dg.part_db;
+    a->ru_w1_hi = o.ru.w1_hi; a->ru_w1_lo = o.ru.w1_lo; a->ru_bias2 = o.ru.bias2; a->ru_a2 = o.ru.a2; a->ru_ib2 = o.ru.ib2; a->ru_h = o.ru.h;
+    return 0;
+}
+
+// want: < 0 the rule, 0 no split, n >= 2 exactly n splits.  Returns the split count (1: none), or -1 for a forced count the launch cannot have
+// (a kernel that does not split, more splits than chunks, or a count that would leave a split without chunks).  *ws_floats: the slabs' size.
+static int sat_bf_split_decide(const SatConvBfLaunch& a, const SatBfKernel& k, int want, int cus, int* cps, long long* ws_floats) {
+    const int tiles = k.slab ? (a.cout_pad / k.co_t) * sat_cdiv(a.nq, k.t_t) * a.p.B : 0, nchunks = sat_cdiv(a.cin_v, k.chunk);
+    int n = 1;
+    *cps = 0;
+    *ws_floats = 0;
+    if (want == 0 || want == 1) return 1;
+    if (want < 0) {
+        if (tiles == 0) return 1;
+        n = sat_conv_split_rule(tiles, nchunks, k.resident, cus > 0 ? cus : sat_cu_count());
+        if (n < 2) return 1;
+    } else {
+        if (tiles == 0 || want > SAT_SPLIT_MAX || want > nchunks) return -1;
+        if (sat_cdiv(nchunks, sat_cdiv(nchunks, want)) != want) return -1;
+        n = want;
+    }
+    *cps = sat_cdiv(nchunks, n);
+    *ws_floats = (long long)tiles * n * k.slab;
+    return n;
+}
+
+static int sat_bf_launch_one(const char* who, SatConvBfLaunch& a, const SatBfKernel& k, void* stream) {
+    const unsigned zmul = (a.nsplit > 1 && a.cps > 0) ? (unsigned)a.nsplit : 1u;      // workgroups per tile
+    if (k.id != SAT_BF_GENERIC) {
+        if (k.id == SAT_BF_K7) sat_bf_launch_k7(a, stream);
+        else sat_bf_launch_k7q(a, stream, zmul);
+        return sat_check_launch(who);
+    }
+    // the generic kernel stages the input's SnakeBeta constants of ALL channels in LDS: 1024 channels on the k = 1 plan (4, 4), 2048 on the others
+    // (every Oobleck level: channels 128 x c_mults <= 16)
+    if (a.p.alpha && a.p.Cin > ((k.ng == 4) ? 1024 : 2048))
+        return sat_bf_fail(who, "an activated input of more than 2048 channels (1024 for K <= 4 at stride 1) is not served by the bf16x3 kernels (ops.use_bf16x3 = False takes the fp32-MFMA ones)");
+    dim3 grid(sat_cdiv(a.nq, k.t_t), a.cout_pad / k.co_t, a.p.B * zmul);
+    if (k.strided) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 4, true>), grid, dim3(256), stream, a); }     // strided: always plan (8, 4)
+    else if (k.ng == 8 && k.cs == 1) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 1, false>), grid, dim3(256), stream, a); }
+    else if (k.ng == 8 && k.cs == 2) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 2, false>), grid, dim3(256), stream, a); }
+    else if (k.ng == 8 && k.cs == 4) { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<8, 4, false>), grid, dim3(256), stream, a); }
+    else { SAT_LAUNCH((sat_conv1d_bf16x3_kernel<4, 4, false>), grid, dim3(256), stream, a); }
+    return sat_check_launch(who);
+}
+
+// the split state of one call through a _ws entry point; the plain entry points pass SAT_NO_SPLIT: no workspace, no split
+struct SatSplitWs { float* ws; long long ws_floats; int want; int cus; };
+static const SatSplitWs SAT_NO_SPLIT{nullptr, 0, 0, 0};
+
+static int sat_bf_run(const char* who, const SatBfShape& s, const SatBfOperands& o, const SatSplitWs& sw, void* stream) {
+    SatBfPlan pl;
+    SatConvBfLaunch a;
+    if (sat_bf_geometry(who, s, &pl, &a)) return 1;
+    const SatBfKernel k = sat_bf_kernel(s.kind, pl, a);
+    if (sat_bf_bind(who, k, o, &a)) return 1;
+    int cps;
+    long long need;
+    const int n = sat_bf_split_decide(a, k, sw.want, sw.cus, &cps, &need);
+    if (n < 0) return sat_bf_fail(who, "this launch cannot be split that many ways (2 <= n <= chunks, every split at least one chunk; the direct k7 kernel and the fused unit do not split)");
+    if (n < 2) return sat_bf_launch_one(who, a, k, stream);
+    if (!sw.ws || sw.ws_floats < need || ((uintptr_t)sw.ws & 15)) return sat_bf_fail(who, "the split workspace is missing, misaligned or smaller than sat_conv_bf16x3_split asks for");
+    a.ws = sw.ws;
+    a.nsplit = n;
+    a.cps = cps;                                           // split launch: n workgroups per tile
+    if (const int st = sat_bf_launch_one(who, a, k, stream)) return st;
+    a.cps = 0;                                             // finish launch: the slabs' sum and the epilogue
+    return sat_bf_launch_one(who, a, k, stream);
+}
+
+// Same contract as sat_conv1d (y[co][t] = sum W[co][ci][k] act(x)[ci][t*stride + k*dil - pad]), with the weights given
+// as sat_pack_weights_bf16x3 planes (mode 0, or mode 1 for a stride-1 data-gradient) and the SnakeBeta constants given
+// pre-exponentiated (sat_snake_consts), or NULL for no activation.  stride 1: K <= 8; stride S: K == 2S, S a power of two.
+extern "C" int sat_conv1d_bf16x3(const float* x, const short* w_hi, const short* w_lo, const float* bias,
+                                 const float* snake_a, const float* snake_ib, const float* res, float* y,
+                                 const float* x2, const float* alpha2, const float* beta2, float* part_da,
+                                 float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil,
+                                 int pad, int tanh_out, void* stream) {
+    const SatBfShape s{SAT_BF_CONV, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, tanh_out, 0, 0};
+    const SatBfOperands o{{x, snake_a, snake_ib}, {}, w_hi, w_lo, {bias, res, y}, {x2, alpha2, beta2, part_da, part_db}, {}, {}};
+    return sat_bf_run("sat_conv1d_bf16x3", s, o, SAT_NO_SPLIT, stream);
+}
+// sat_conv1d_bf16x3 that ALSO writes act(y) as the activation planes of the k7 conv that consumes y next (sat_conv1d_bf16x3_planesq):
+// em_hi / em_lo [B][ceil(Cout/8)][em_rows][8] bf16 (row 32 + t; the caller keeps the rows around the sequence zero),
+// em_a / em_ib the consumer's pre-exponentiated SnakeBeta constants (sat_snake_consts) or NULL for planes of y itself.  The k = 1 /
+// K <= 4 / strided plans only (the producers of a ResidualUnit's input), Tout % 4 == 0.
+extern "C" int sat_conv1d_bf16x3_emit(const float* x, const short* w_hi, const short* w_lo, const float* bias,
+                                      const float* snake_a, const float* snake_ib, const float* res, float* y,
+                                      const float* x2, const float* alpha2, const float* beta2, float* part_da,
+                                      float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil,
+                                      int pad, int tanh_out, void* em_hi, void* em_lo, const float* em_a, const float* em_ib, int em_rows,
+                                      void* stream) {
+    if (!em_hi) return sat_bf_fail("sat_conv1d_bf16x3_emit", "planes missing");
+    const SatBfShape s{SAT_BF_CONV, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, tanh_out, 0, 0};
+    const SatBfOperands o{{x, snake_a, snake_ib}, {}, w_hi, w_lo, {bias, res, y}, {x2, alpha2, beta2, part_da, part_db},
+                          {(short*)em_hi, (short*)em_lo, em_a, em_ib, em_rows}, {}};
+    return sat_bf_run("sat_conv1d_bf16x3_emit", s, o, SAT_NO_SPLIT, stream);
+}
+// sat_conv1d_bf16x3 / _emit (em_hi NULL: no emission) that may SPLIT its launch over input-channel chunks (sat_conv_split_rule): ws = a workspace of
+// ws_floats floats, at least what sat_conv_bf16x3_split(0, ...) reports for the same `split` (-1: the rule, 0: off, n >= 2: exactly n — status 1
+// and no launch where the launch cannot be split that way).  The workspace is written by the first launch and read by the second.
+extern "C" int sat_conv1d_bf16x3_ws(const float* x, const short* w_hi, const short* w_lo, const float* bias,
+                                    const float* snake_a, const float* snake_ib, const float* res, float* y,
+                                    const float* x2, const float* alpha2, const float* beta2, float* part_da,
+                                    float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil,
+                                    int pad, int tanh_out, void* em_hi, void* em_lo, const float* em_a, const float* em_ib, int em_rows,
+                                    float* ws, long long ws_floats, int split, void* stream) {
+    const SatBfShape s{SAT_BF_CONV, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, tanh_out, 0, 0};
+    const SatBfOperands o{{x, snake_a, snake_ib}, {}, w_hi, w_lo, {bias, res, y}, {x2, alpha2, beta2, part_da, part_db},
+                          {(short*)em_hi, (short*)em_lo, em_a, em_ib, em_rows}, {}};
+    return sat_bf_run("sat_conv1d_bf16x3_ws", s, o, SatSplitWs{ws, ws_floats, split, 0}, stream);
+}
+
 // sat_conv1d_bf16x3 for stride 1, 5 <= K <= 7, with the (activated) input given as planes (sat_conv1d_k7_planes or a producer's emission)
 // and the weights packed by sat_pack_weights_k7q (mode 0, or mode 1 for a data-gradient): conv1d_bf16x3_k7q.h.
-static int sat_conv1d_bf16x3_planesq_impl(const char* what, const short* xp_hi, const short* xp_lo, int rows, const short* w_hi, const short* w_lo,
-                                          const float* bias, const float* res, float* y, const float* x2, const float* alpha2,
-                                          const float* beta2, float* part_da, float* part_db, int B, int Cin, int Cout, int Tin, int Tout,
-                                          int K, int dil, int pad, int tanh_out, int flags, void* stream, const SatSplitWs& sw = SAT_NO_SPLIT,
-                                          SatConvBfLaunch* geom_only = nullptr) {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || Tin <= 0 || Tout <= 0) { sat_set_error("sat_conv1d_bf16x3_planesq: empty shape"); return 1; }
-    if (K < 5 || K > SAT_K7Q_TAPS || dil < 1 || (K - 1) * dil > 62) {
-        sat_set_error("sat_conv1d_bf16x3_planesq: needs stride 1, 5 <= K <= 7, (K-1)*dil <= 62");
-        return 1;
-    }
-    if (rows < sat_conv1d_k7_plane_rows(Tin, Tout, pad)) { sat_set_error("sat_conv1d_bf16x3_planesq: rows must be >= sat_conv1d_k7_plane_rows(Tin, Tout, pad)"); return 1; }
-    if (x2 && (!alpha2 || !beta2 || !part_da || !part_db)) { sat_set_error("sat_conv1d_bf16x3_planesq: backward epilogue needs alpha2/beta2/partials"); return 1; }
-    SatConvBfLaunch a;
-    a.p = SatConvParams{nullptr, nullptr, bias, nullptr, nullptr, res, y, x2, alpha2, beta2, part_da, part_db,
-                        B, Cin, Cout, Tin, Tout, K, 1, dil, pad, tanh_out};
-    a.w_hi = w_hi;
-    a.w_lo = w_lo;
-    a.cout_v = Cout;
-    a.cout_pad = sat_cdiv(Cout, SAT_CO_T) * SAT_CO_T;
-    a.cin_v = Cin;
-    a.sin_log2 = 0;
-    a.sout_log2 = 0;
-    a.in_shift = 0;
-    a.out_shift = 0;
-    a.nq = Tout;
-    a.xp_hi = xp_hi;
-    a.xp_lo = xp_lo;
-    a.xp_rows = rows;
-    a.xp_c8 = sat_cdiv(Cin, 8);
-    a.wq = 1;
-    a.dma_in_mfma = (flags & 4) ? 1 : 0;                     // flags bit 2: VARIANT 3 of the k7q kernel
-    a.persist = (flags & 1) ? 0 : ((flags & 2) ? 2 : 1);      // flags bit 0: one workgroup per tile (round 5's launch; A/B runs and the tests'
-                                                              // second arm); bit 1: persistent at any size (the tests: small shapes)
-    SatBfPlan pl{8, 1, K};
-    if (geom_only) { *geom_only = a; return 0; }
-    return sat_bf_launch(what, a, pl, stream, sw);
-}
 extern "C" int sat_conv1d_bf16x3_planesq(const short* xp_hi, const short* xp_lo, int rows, const short* w_hi, const short* w_lo,
                                          const float* bias, const float* res, float* y, const float* x2, const float* alpha2,
                                          const float* beta2, float* part_da, float* part_db, int B, int Cin, int Cout, int Tin, int Tout,
                                          int K, int dil, int pad, int tanh_out, int flags, void* stream) {
-    return sat_conv1d_bf16x3_planesq_impl("sat_conv1d_bf16x3_planesq", xp_hi, xp_lo, rows, w_hi, w_lo, bias, res, y, x2, alpha2, beta2, part_da, part_db,
-                                          B, Cin, Cout, Tin, Tout, K, dil, pad, tanh_out, flags, stream);
+    const SatBfShape s{SAT_BF_PLANES, B, Cin, Cout, Tin, Tout, K, 1, dil, pad, tanh_out, rows, flags};
+    const SatBfOperands o{{}, {xp_hi, xp_lo}, w_hi, w_lo, {bias, res, y}, {x2, alpha2, beta2, part_da, part_db}, {}, {}};
+    return sat_bf_run("sat_conv1d_bf16x3_planesq", s, o, SAT_NO_SPLIT, stream);
 }
 // sat_conv1d_bf16x3_planesq that may split its launch: ws / ws_floats / split as sat_conv1d_bf16x3_ws (sat_conv_bf16x3_split(2, ...)).  A split launch
 // is one workgroup per (tile, split), whatever the persistence flags say.
@@ -921,8 +971,9 @@ extern "C" int sat_conv1d_bf16x3_planesq_ws(const short* xp_hi, const short* xp_
                                             const float* bias, const float* res, float* y, const float* x2, const float* alpha2,
                                             const float* beta2, float* part_da, float* part_db, int B, int Cin, int Cout, int Tin, int Tout,
                                             int K, int dil, int pad, int tanh_out, int flags, float* ws, long long ws_floats, int split, void* stream) {
-    return sat_conv1d_bf16x3_planesq_impl("sat_conv1d_bf16x3_planesq_ws", xp_hi, xp_lo, rows, w_hi, w_lo, bias, res, y, x2, alpha2, beta2, part_da, part_db,
-                                          B, Cin, Cout, Tin, Tout, K, dil, pad, tanh_out, flags, stream, SatSplitWs{ws, ws_floats, split, 0});
+    const SatBfShape s{SAT_BF_PLANES, B, Cin, Cout, Tin, Tout, K, 1, dil, pad, tanh_out, rows, flags};
+    const SatBfOperands o{{}, {xp_hi, xp_lo}, w_hi, w_lo, {bias, res, y}, {x2, alpha2, beta2, part_da, part_db}, {}, {}};
+    return sat_bf_run("sat_conv1d_bf16x3_planesq_ws", s, o, SatSplitWs{ws, ws_floats, split, 0}, stream);
 }
 
 // The whole ResidualUnit forward in one launch (autoencoders.py:58-83), C <= 128 channels:
@@ -934,74 +985,22 @@ extern "C" int sat_residual_unit_fwd(const short* xp_hi, const short* xp_lo, int
                                      const float* bias1, const float* a2, const float* ib2, const short* w1_hi, const short* w1_lo,
                                      const float* bias2, const float* x, float* h, float* y, int B, int C, int T, int K, int dil, int pad,
                                      void* em_hi, void* em_lo, const float* em_a, const float* em_ib, int em_rows, void* stream) {
-    if (B <= 0 || C <= 0 || T <= 0 || C > SAT_K7_CO) { sat_set_error("sat_residual_unit_fwd: needs 1 <= C <= 128"); return 1; }
-    if (K < 5 || K > SAT_K7Q_TAPS || dil < 1 || (K - 1) * dil > 62 || 2 * pad != (K - 1) * dil) {
-        sat_set_error("sat_residual_unit_fwd: needs 5 <= K <= 7, (K-1)*dil <= 62, 'same' padding");
-        return 1;
-    }
-    if (rows < sat_conv1d_k7_plane_rows(T, T, pad)) { sat_set_error("sat_residual_unit_fwd: rows must be >= sat_conv1d_k7_plane_rows(T, T, pad)"); return 1; }
-    if (!xp_hi || !xp_lo || !w7_hi || !w7_lo || !w1_hi || !w1_lo || !a2 || !ib2 || !x || !y) { sat_set_error("sat_residual_unit_fwd: missing operand"); return 1; }
-    if ((T & 3) || (((uintptr_t)y | (uintptr_t)x) & 15)) { sat_set_error("sat_residual_unit_fwd: T % 4 == 0 and 16-byte aligned x / y"); return 1; }
-    SatConvBfLaunch a;
-    a.p = SatConvParams{nullptr, nullptr, bias1, nullptr, nullptr, x, y, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        B, C, C, T, T, K, 1, dil, pad, 0};
-    a.w_hi = w7_hi;
-    a.w_lo = w7_lo;
-    a.cout_v = C;
-    a.cout_pad = SAT_CO_T;
-    a.cin_v = C;
-    a.sin_log2 = 0; a.sout_log2 = 0; a.in_shift = 0; a.out_shift = 0;
-    a.nq = T;
-    a.xp_hi = xp_hi; a.xp_lo = xp_lo; a.xp_rows = rows; a.xp_c8 = sat_cdiv(C, 8);
-    a.wq = 1;
-    a.ru_w1_hi = w1_hi; a.ru_w1_lo = w1_lo; a.ru_bias2 = bias2; a.ru_a2 = a2; a.ru_ib2 = ib2; a.ru_h = h;
-    if (em_hi) {
-        if (!em_lo || (em_a == nullptr) != (em_ib == nullptr) || em_rows < SAT_K7P_LEAD_ROWS + T || (((uintptr_t)em_hi | (uintptr_t)em_lo) & 15)) {
-            sat_set_error("sat_residual_unit_fwd: bad emission planes");
-            return 1;
-        }
-        a.em_hi = (short*)em_hi; a.em_lo = (short*)em_lo; a.em_a = em_a; a.em_ib = em_ib; a.em_rows = em_rows; a.em_c8 = sat_cdiv(C, 8);
-    }
-    SatBfPlan pl{8, 1, K};
-    return sat_bf_launch("sat_residual_unit_fwd", a, pl, stream);
+    const SatBfShape s{SAT_BF_UNIT, B, C, C, T, T, K, 1, dil, pad, 0, rows, 0};
+    const SatBfOperands o{{}, {xp_hi, xp_lo}, w7_hi, w7_lo, {bias1, x, y}, {}, {(short*)em_hi, (short*)em_lo, em_a, em_ib, em_rows},
+                          {w1_hi, w1_lo, bias2, a2, ib2, h}};
+    return sat_bf_run("sat_residual_unit_fwd", s, o, SAT_NO_SPLIT, stream);
 }
 
 // Same contract as sat_convtr1d (y[co][q*stride + k - pad] += W[ci][co][k] act(x)[ci][q], K == 2*stride, power-of-two
 // stride), weights as sat_pack_weights_bf16x3 planes (mode 2).
-static int sat_convtr1d_bf16x3_impl(const char* what, const float* x, const short* w_hi, const short* w_lo, const float* bias,
-                                    const float* snake_a, const float* snake_ib, const float* res, float* y,
-                                    const float* x2, const float* alpha2, const float* beta2, float* part_da,
-                                    float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride,
-                                    int pad, int tanh_out, void* stream, const SatSplitWs& sw = SAT_NO_SPLIT, SatConvBfLaunch* geom_only = nullptr,
-                                    SatBfPlan* plan_out = nullptr) {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || Tin <= 0 || Tout <= 0) { sat_set_error("sat_convtr1d_bf16x3: empty shape"); return 1; }
-    SatBfPlan pl;
-    if (!sat_bf_plan(K, stride, 2, &pl) || pad < 0) { sat_set_error("sat_convtr1d_bf16x3: needs K == 2*stride with a power-of-two stride"); return 1; }
-    if ((snake_a == nullptr) != (snake_ib == nullptr)) { sat_set_error("sat_convtr1d_bf16x3: snake constants must both be given"); return 1; }
-    if (x2 && (!alpha2 || !beta2 || !part_da || !part_db)) { sat_set_error("sat_convtr1d_bf16x3: backward epilogue needs alpha2/beta2/partials"); return 1; }
-    SatConvBfLaunch a;
-    a.p = SatConvParams{x, nullptr, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
-                        B, Cin, Cout, Tin, Tout, 2, 1, 1, 1, tanh_out};
-    a.w_hi = w_hi;
-    a.w_lo = w_lo;
-    a.cout_v = Cout * stride;
-    a.cout_pad = sat_cdiv(a.cout_v, SAT_CO_T) * SAT_CO_T;
-    a.cin_v = Cin;
-    a.sin_log2 = 0;
-    a.sout_log2 = sat_log2i(stride);
-    a.in_shift = 0;
-    a.out_shift = pad;
-    a.nq = sat_cdiv(Tout + pad, stride);
-    if (geom_only) { *geom_only = a; *plan_out = pl; return 0; }
-    return sat_bf_launch(what, a, pl, stream, sw);
-}
 extern "C" int sat_convtr1d_bf16x3(const float* x, const short* w_hi, const short* w_lo, const float* bias,
                                    const float* snake_a, const float* snake_ib, const float* res, float* y,
                                    const float* x2, const float* alpha2, const float* beta2, float* part_da,
                                    float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride,
                                    int pad, int tanh_out, void* stream) {
-    return sat_convtr1d_bf16x3_impl("sat_convtr1d_bf16x3", x, w_hi, w_lo, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
-                                    B, Cin, Cout, Tin, Tout, K, stride, pad, tanh_out, stream);
+    const SatBfShape s{SAT_BF_CONVTR, B, Cin, Cout, Tin, Tout, K, stride, 1, pad, tanh_out, 0, 0};
+    const SatBfOperands o{{x, snake_a, snake_ib}, {}, w_hi, w_lo, {bias, res, y}, {x2, alpha2, beta2, part_da, part_db}, {}, {}};
+    return sat_bf_run("sat_convtr1d_bf16x3", s, o, SAT_NO_SPLIT, stream);
 }
 // sat_convtr1d_bf16x3 that may split its launch: ws / ws_floats / split as sat_conv1d_bf16x3_ws (sat_conv_bf16x3_split(1, ...))
 extern "C" int sat_convtr1d_bf16x3_ws(const float* x, const short* w_hi, const short* w_lo, const float* bias,
@@ -1009,52 +1008,40 @@ extern "C" int sat_convtr1d_bf16x3_ws(const float* x, const short* w_hi, const s
                                       const float* x2, const float* alpha2, const float* beta2, float* part_da,
                                       float* part_db, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride,
                                       int pad, int tanh_out, float* ws, long long ws_floats, int split, void* stream) {
-    return sat_convtr1d_bf16x3_impl("sat_convtr1d_bf16x3_ws", x, w_hi, w_lo, bias, snake_a, snake_ib, res, y, x2, alpha2, beta2, part_da, part_db,
-                                    B, Cin, Cout, Tin, Tout, K, stride, pad, tanh_out, stream, SatSplitWs{ws, ws_floats, split, 0});
+    const SatBfShape s{SAT_BF_CONVTR, B, Cin, Cout, Tin, Tout, K, stride, 1, pad, tanh_out, 0, 0};
+    const SatBfOperands o{{x, snake_a, snake_ib}, {}, w_hi, w_lo, {bias, res, y}, {x2, alpha2, beta2, part_da, part_db}, {}, {}};
+    return sat_bf_run("sat_convtr1d_bf16x3_ws", s, o, SatSplitWs{ws, ws_floats, split, 0}, stream);
 }
-// How many ways the launch of a conv splits, and the workspace that takes: kind 0 = sat_conv1d_bf16x3 (Tin = Tout * stride is assumed: the count
-// does not depend on Tin), 1 = sat_convtr1d_bf16x3, 2 = sat_conv1d_bf16x3_planesq (stride ignored).  split: -1 the rule (sat_conv_split_rule), 0 off,
+
+// How many ways the launch of a conv splits, and the workspace that takes: kind 0 = sat_conv1d_bf16x3, 1 = sat_convtr1d_bf16x3, 2 =
+// sat_conv1d_bf16x3_planesq (stride ignored); the count does not depend on Tin.  split: -1 the rule (sat_conv_split_rule), 0 off,
 // n >= 2 forced; cus: the CU count the rule assumes (<= 0: this device's).  Returns the split count (1: a plain launch), -1 where the shape is not
 // served or a forced count is not possible; *ws_floats (may be NULL): floats of workspace the _ws entry point needs.  Host code only.
 extern "C" int sat_conv_bf16x3_split(int kind, int B, int Cin, int Cout, int Tout, int K, int stride, int dil, int pad, int split, int cus,
                                      long long* ws_floats) {
-    SatConvBfLaunch a;
-    SatBfPlan pl{8, 1, K};
-    int st = 1;
-    const float* one = reinterpret_cast<const float*>(16);       // (stands for "given" where the argument checks ask; never dereferenced)
     if (ws_floats) *ws_floats = 0;
-    if (kind == 0) {
-        const int Tin = (Tout - 1) * stride + dil * (K - 1) + 1 - 2 * pad;
-        st = sat_conv1d_bf16x3_impl("sat_conv_bf16x3_split", nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, B, Cin, Cout, Tin > 0 ? Tin : 1, Tout, K, stride, dil, pad, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                                    SAT_NO_SPLIT, &a, &pl);
-    } else if (kind == 1) {
-        st = sat_convtr1d_bf16x3_impl("sat_conv_bf16x3_split", nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                      nullptr, nullptr, B, Cin, Cout, 1, Tout, K, stride, pad, 0, nullptr, SAT_NO_SPLIT, &a, &pl);
-    } else if (kind == 2) {
-        const int rows = sat_conv1d_k7_plane_rows(Tout, Tout, pad);
-        st = sat_conv1d_bf16x3_planesq_impl("sat_conv_bf16x3_split", reinterpret_cast<const short*>(one), reinterpret_cast<const short*>(one), rows, nullptr,
-                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, Cin, Cout, Tout, Tout, K, dil,
-                                            pad, 0, 0, nullptr, SAT_NO_SPLIT, &a);
-    } else {
-        sat_set_error("sat_conv_bf16x3_split: kind 0 | 1 | 2");
-    }
-    if (st != 0) return -1;
+    if (kind < SAT_BF_CONV || kind > SAT_BF_PLANES) { sat_set_error("sat_conv_bf16x3_split: kind 0 | 1 | 2"); return -1; }
+    const SatBfShape s{kind, B, Cin, Cout, Tout, Tout, K, stride, dil, pad, 0, kind == SAT_BF_PLANES ? sat_conv1d_k7_plane_rows(Tout, Tout, pad) : 0, 0};
+    SatBfPlan pl;
+    SatConvBfLaunch a;
+    if (sat_bf_geometry("sat_conv_bf16x3_split", s, &pl, &a)) return -1;
     int cps;
     long long need;
-    const int n = sat_bf_split_decide(a, pl, split, cus, &cps, &need);
+    const int n = sat_bf_split_decide(a, sat_bf_kernel(kind, pl, a), split, cus, &cps, &need);
     if (n < 0) { sat_set_error("sat_conv_bf16x3_split: this launch cannot be split that many ways"); return -1; }
     if (ws_floats) *ws_floats = need;
     return n;
 }
-// rows of the snake-gradient partial-sum planes written by sat_conv1d_bf16x3 (one per batch item and time tile)
+// rows of the snake-gradient partial-sum planes written by sat_conv1d_bf16x3 (one per batch item and time tile of the launch's kernel)
 extern "C" int sat_conv1d_bf16x3_partial_rows(int B, int Tout, int K, int stride) {
+    const SatBfShape s{SAT_BF_CONV, B, 1, 1, Tout, Tout, K, stride, 1, 0, 0, 0, 0};
     SatBfPlan pl;
-    if (B <= 0 || Tout <= 0 || !sat_bf_plan(K, stride, 0, &pl)) return -1;
-    const bool k7 = pl.ng == 8 && pl.cs == 1 && stride == 1;
-    return B * sat_cdiv(Tout, k7 ? SAT_K7_T : SAT_T_T);
+    SatConvBfLaunch a;
+    if (sat_bf_geometry("sat_conv1d_bf16x3_partial_rows", s, &pl, &a)) return -1;
+    return B * sat_cdiv(a.nq, sat_bf_kernel(s.kind, pl, a).t_t);
 }
+// (answers for any stride >= 1, as it always has: the transposed plan's kernel is the generic one at every stride)
 extern "C" int sat_convtr1d_bf16x3_partial_rows(int B, int Tout, int stride, int pad) {
     if (B <= 0 || Tout <= 0 || stride < 1 || pad < 0) return -1;
-    return B * sat_cdiv(sat_cdiv(Tout + pad, stride), SAT_T_T);
+    return B * sat_cdiv(sat_cdiv(Tout + pad, stride), sat_bf_kernel(SAT_BF_CONVTR, SatBfPlan{8, 4, 2}, SatConvBfLaunch{}).t_t);
 }

@@ -480,7 +480,7 @@ __global__ void __launch_bounds__(SAT_K7_NT) sat_conv1d_bf16x3_k7q_kernel(SatCon
   }
 }
 
-// zmul: workgroups per tile (the split launch of sat_bf_launch: SatConvBfLaunch::nsplit; 1 otherwise)
+// zmul: workgroups per tile (the split launch of sat_bf_run: SatConvBfLaunch::nsplit; 1 otherwise)
 static void sat_bf_launch_k7q(SatConvBfLaunch& a, void* stream, unsigned zmul = 1) {
     const long long total = (long long)(a.cout_pad / SAT_K7_CO) * sat_cdiv(a.nq, SAT_K7_T) * a.p.B;
     a.stagger = 1;                                         // measured: -1 % forward, -2.5 % data-gradient (tools/kq_ab.py); 2 and 4 lose

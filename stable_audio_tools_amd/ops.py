@@ -385,32 +385,47 @@ class SatOps:
         st = self._stream(x)
         return self._workspace(("conv_split", shape, n, x.device, st.value if st is not None else 0), need, torch.float32, x.device), n
 
-    def _bf16x3_call(self, fn, rows, x, w_planes, cout, tout, dims, bias, snake, res, tanh_out, dsnake, out=None, sconsts=None, emit=None):
+    # kind (as sat_conv_bf16x3_split: 0 conv, 1 transposed conv, 2 plane-fed k7 conv) -> its (plain, emitting, splitting) entry points.  NAMES,
+    # looked up on self.lib at every call: bench.py's conv profiler and the parity tests replace attributes of ops.lib after SatOps is built.
+    _BF16X3_ENTRY = {0: ("sat_conv1d_bf16x3", "sat_conv1d_bf16x3_emit", "sat_conv1d_bf16x3_ws"),
+                     1: ("sat_convtr1d_bf16x3", None, "sat_convtr1d_bf16x3_ws"),
+                     2: ("sat_conv1d_bf16x3_planesq", None, "sat_conv1d_bf16x3_planesq_ws")}
+
+    def _bf16x3_conv(self, kind, rows, x, w_planes, cout, tout, dims, bias, snake, res, tanh_out, dsnake, out=None, sconsts=None, emit=None,
+                     keep_planes=False):
+        """One bf16x3 conv call of `kind`; dims = (k, stride, dil, pad), rows = its *_partial_rows.  A launch that splits goes through the _ws
+        entry point, one that emits through _emit, every other one through the plain entry point."""
         b, cin, tin = x.shape
-        transposed = len(dims) == 3                     # (k, stride, pad): sat_convtr1d_bf16x3; (k, stride, dil, pad): sat_conv1d_bf16x3
+        k, stride, dil, pad = dims
         self._f32(x, bias, res)
         sa = sib = None
         if snake is not None:
             sa, sib = sconsts if sconsts is not None else self.snake_consts(snake[0], snake[1])
+        st = self._stream(x)
+        xp, kept = self._k7_input_planes(x, snake, sa, sib, cout, tout, k, pad, st, keep_planes) if kind == 2 else (None, None)
         y = self._conv_out(out, b, cout, tout, x.device)
         x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, rows, x.device)
-        ep, ea, eib = self._emit_args(emit, b, cout, tout, x.device, self._stream(x))
-        args = (_ptr(x), _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(sa), _ptr(sib),
-                _ptr(res), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb),
-                b, cin, cout, tin, tout, *dims, int(tanh_out))
-        slabs, split = self._conv_split_ws(1 if transposed else 0, x, cout, tout, dims[0], dims[1], 1 if transposed else dims[2], dims[-1])
-        if slabs is not None and transposed:
-            self._chk(self.lib.sat_convtr1d_bf16x3_ws(*args, _ptr(slabs), slabs.numel(), split, self._stream(x)))
-        elif slabs is not None:
-            self._chk(self.lib.sat_conv1d_bf16x3_ws(*args, _ptr(ep.hi), _ptr(ep.lo), _ptr(ea), _ptr(eib), ep.rows, _ptr(slabs), slabs.numel(), split,
-                                                    self._stream(x)))
-        elif emit:
-            # plane emission (sat_conv1d_bf16x3_emit): the planes the k7 conv that consumes y next would otherwise build in a pre-pass
-            self._chk(self.lib.sat_conv1d_bf16x3_emit(*args, _ptr(ep.hi), _ptr(ep.lo), _ptr(ea), _ptr(eib), ep.rows, self._stream(x)))
+        ep, ea, eib = self._emit_args(emit, b, cout, tout, x.device, st)
+        w = (_ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias))
+        tail = (_ptr(res), _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb), b, cin, cout, tin, tout, k)
+        if kind == 2:
+            args = (_ptr(xp.hi), _ptr(xp.lo), xp.rows, *w, *tail, dil, pad, int(tanh_out),
+                    {True: 0, False: 1, "force": 2}[self.k7q_persist] | (4 if self.k7q_dma_in_mfma else 0))
         else:
-            self._chk(fn(*args, self._stream(x)))
+            args = (_ptr(x), *w, _ptr(sa), _ptr(sib), *tail, stride, *((dil,) if kind == 0 else ()), pad, int(tanh_out))
+        plain, emitting, splitting = self._BF16X3_ENTRY[kind]
+        # plane emission: the planes the k7 conv that consumes y next would otherwise build in a pre-pass (arguments of _emit, and of the conv's _ws)
+        em = (_ptr(ep.hi), _ptr(ep.lo), _ptr(ea), _ptr(eib), ep.rows) if emitting else ()
+        slabs, split = self._conv_split_ws(kind, x, cout, tout, k, stride, dil, pad)
+        if slabs is not None:
+            self._chk(getattr(self.lib, splitting)(*args, *em, _ptr(slabs), slabs.numel(), split, st))
+        elif emit:
+            self._chk(getattr(self.lib, emitting)(*args, *em, st))
+        else:
+            self._chk(getattr(self.lib, plain)(*args, st))
         self._emit_done(emit, y, ep)
-        return self._dsnake_result(y, pda, pdb)
+        y = self._dsnake_result(y, pda, pdb)
+        return (y, kept) if keep_planes else y
 
     # ---- fused ResidualUnit forward (csrc/conv1d_bf16x3_k7q.h, FUSED): one launch for snake -> conv7 -> snake -> conv1 -> + x ----
     ru_fused = True
@@ -456,7 +471,7 @@ class SatOps:
         return h, y
 
     # ---- the activation planes of the k = 7 convs, and the dh that exists only as planes -------------------------------------------
-    # The k = 7 convs of the ResidualUnits (_k7_planes_call, residual_unit_fwd) read act(x) as pre-split bf16 hi / lo Planes, from one of:
+    # The k = 7 convs of the ResidualUnits (_bf16x3_conv kind 2, residual_unit_fwd) read act(x) as pre-split bf16 hi / lo Planes, from one of:
     #  * EMISSION: the producer of x wrote them in its epilogue (emit=) into the shared pair of its output shape (_emit_planes; the workspace
     #    cache owns it) or, where the consumer owns a buffer, into that; _emitted holds them for the ONE conv that takes x next;
     #  * the PRE-PASS (_k7_prepass): one conversion launch into the shared workspace, valid for the conv enqueued right behind it;
@@ -599,19 +614,13 @@ class SatOps:
         if len(w_planes) == 3:          # sat_pack_weights_k7q layout (pack_bf16x3(q=True) after k7q_applicable)
             if not (stride == 1 and 5 <= k <= 7 and 0 <= pad <= 32 and (k - 1) * dil <= 62):
                 raise ValueError("conv1d_bf16x3: q-packed weights need stride 1, 5 <= K <= 7, pad <= 32, (K-1)*dil <= 62")
-            return self._k7_planes_call(rows, x, w_planes, cout, tout, k, dil, pad, bias, snake, res, tanh_out, dsnake, out, sconsts, keep_planes)
-        y = self._bf16x3_call(self.lib.sat_conv1d_bf16x3, rows, x, w_planes, cout, tout, (k, stride, dil, pad),
-                              bias, snake, res, tanh_out, dsnake, out, sconsts, emit)
-        return (y, None) if keep_planes else y
+            return self._bf16x3_conv(2, rows, x, w_planes, cout, tout, (k, 1, dil, pad), bias, snake, res, tanh_out, dsnake, out, sconsts, None, keep_planes)
+        return self._bf16x3_conv(0, rows, x, w_planes, cout, tout, (k, stride, dil, pad), bias, snake, res, tanh_out, dsnake, out, sconsts, emit, keep_planes)
 
-    def _k7_planes_call(self, prows, x, w_planes, cout, tout, k, dil, pad, bias, snake, res, tanh_out, dsnake, out=None, sconsts=None,
-                        keep_planes=False):
+    def _k7_input_planes(self, x, snake, sa, sib, cout, tout, k, pad, st, keep_planes):
+        """-> (the Planes of act(x) a plane-fed k7 conv reads, what it keeps of them for its backward or None): emitted ones, the conv's own
+        buffer or the shared pre-pass — the comment above _NO_PLANES."""
         b, cin, tin = x.shape
-        self._f32(x, bias, res)
-        sa = sib = None
-        if snake is not None:
-            sa, sib = sconsts if sconsts is not None else self.snake_consts(snake[0], snake[1])
-        st = self._stream(x)
         xp = self._take_emitted(x, snake)               # the producer's epilogue already wrote act(x) as planes
         if xp is None:
             self._check_written(x)
@@ -622,19 +631,7 @@ class SatOps:
         elif xp is None:
             xp = self._k7_prepass(x, sa, sib, tout, pad, st)
         # only the k7 C -> C weight gradient reads kept planes, and only from the owned buffer (the first step's are emitted into a shared one: fp32 this once)
-        kept = xp if own is not None and xp.own is own and k == 7 and cout == cin else None
-        y = self._conv_out(out, b, cout, tout, x.device)
-        x2, a2, b2, pda, pdb = self._dsnake_args(dsnake, cout, prows, x.device)
-        args = (_ptr(xp.hi), _ptr(xp.lo), xp.rows, _ptr(w_planes[0]), _ptr(w_planes[1]), _ptr(bias), _ptr(res),
-                _ptr(y), _ptr(x2), _ptr(a2), _ptr(b2), _ptr(pda), _ptr(pdb), b, cin, cout, tin, tout,
-                k, dil, pad, int(tanh_out), {True: 0, False: 1, "force": 2}[self.k7q_persist] | (4 if self.k7q_dma_in_mfma else 0))
-        slabs, split = self._conv_split_ws(2, x, cout, tout, k, 1, dil, pad)
-        if slabs is not None:
-            self._chk(self.lib.sat_conv1d_bf16x3_planesq_ws(*args, _ptr(slabs), slabs.numel(), split, st))
-        else:
-            self._chk(self.lib.sat_conv1d_bf16x3_planesq(*args, st))
-        y = self._dsnake_result(y, pda, pdb)
-        return (y, kept) if keep_planes else y
+        return xp, (xp if own is not None and xp.own is own and k == 7 and cout == cin else None)
 
     def convtr1d_bf16x3(self, x, w_planes, cout, k, stride, pad, tout=None, bias=None, snake=None, res=None,
                         tanh_out=False, dsnake=None, sconsts=None):
@@ -643,8 +640,7 @@ class SatOps:
         if tout is None:
             tout = (tin - 1) * stride - 2 * pad + k
         rows = self.lib.sat_convtr1d_bf16x3_partial_rows(b, tout, stride, pad)
-        return self._bf16x3_call(self.lib.sat_convtr1d_bf16x3, rows, x, w_planes, cout, tout, (k, stride, pad),
-                                 bias, snake, res, tanh_out, dsnake, None, sconsts)
+        return self._bf16x3_conv(1, rows, x, w_planes, cout, tout, (k, stride, 1, pad), bias, snake, res, tanh_out, dsnake, None, sconsts)
 
     def convtr1d(self, x, w_packed, cout, k, stride, pad, tout=None, bias=None, snake=None, res=None,
                  tanh_out=False, dsnake=None):
